@@ -2,7 +2,7 @@
 """bench.py — throughput of the NPLDA hot path on MI355X (BASELINE.json metric: scored trial-pairs/s).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg1|cfg2|cfg3|cfg5] [--scaling weak|strong] [--dim D]
-                    [--emulate-rank r/N]
+                    [--emulate-rank r/N] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 Workloads (BASELINE.json `configs`):
@@ -31,9 +31,20 @@ line says so (`config.emulated_rank`, `n_gpus` 1).
 GPU, RCCL); it exits non-zero if the box has fewer than N devices.  NPLDA_BENCH_BACKEND=gloo is a plumbing dry run on a
 box with fewer GPUs than ranks (ranks share devices; timings meaningless).
 
-Extra objects on the JSON line (tier contract): `roofline` (dominant kernel vs its peak, per-launch duration from HIP
-events on the launch stream), `alt_d170` (the same kernel at the reference's shipped 512->170->170 shape) and
-`cpu_baseline` (the reference's forward restated as torch CPU ops, timed on this box's host cores; rank 0, N = 1 only).
+A plain cfg1 run (`bench.py --gpus N --steps K --warmup W`) does only what its headline needs: set up, W untimed steps,
+K timed steps, the outputs if --dump-outputs is given, the line.  Its `roofline` (dominant kernel vs its peak) comes from
+the HIP events of the timed steps themselves.
+--full adds everything else that has runs of its own, on the same line as before: the shader clock under the kernel and
+`first_call_ms` with the cold-start series, `alt_bf16x3`, `alt_d170` (the same kernel at the reference's shipped
+512->170->170 shape), `cpu_baseline` (the reference's forward restated as torch CPU ops, timed on the host's cores;
+rank 0, N = 1 only), the other BASELINE configs (`alt_cfg2`, `alt_cfg3`, `alt_cfg5`), `alt_dropin` and the secondary
+kernel families at N = 1, the collective-bearing workloads at N > 1, and the full objects in bench_detail.json.
+
+--dump-outputs DIR: after the timed steps, what the timed path returned in its LAST timed step (rank 0's share at N > 1)
+as DIR/<name>.npy, float32 or float64, at most 64 MB in all (a larger array is written as a fixed seeded sample of its
+elements).  The inputs are seeded: the same arguments give the same inputs on every run, so two builds can be compared
+output for output (cfg1 `scores`; cfg3 `normalized_scores`; cfg2 / cfg5 `loss`, the head's parameters after the step and
+cfg5's `dx1`, `dx2` — the training state also depends on how many warm-up steps ran, which the settle time decides).
 """
 import argparse
 import json
@@ -314,6 +325,41 @@ def kernel_ms_of(fn, reps=10, batches=3, warm=3):
     return sorted(ms)[len(ms) // 2], out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+PARAM_NAMES = ("W1", "b1", "W2", "b2", "P_sqrt", "Q")  # NeuralPlda._params() order
+
+
+def keep_outputs(args, **arrays):
+    """--dump-outputs: host copies of what the timed path returned in its last timed step, taken before anything else
+    runs on the device (the training steps return buffers they overwrite); float64 stays float64, the rest is float32.
+    None without the option."""
+    if not getattr(args, "dump_outputs", None):
+        return None
+    out = {}
+    for k, v in arrays.items():
+        v = v.detach()
+        out[k] = (v if v.dtype == torch.float64 else v.float()).cpu().numpy()
+    return out
+
+
+def write_outputs(d, arrays, limit=DUMP_LIMIT_BYTES):
+    """Each array as d/<name>.npy, at most `limit` bytes in all: the smallest arrays are written whole first, and an array
+    larger than its share of what is left is written as a sample — the same seeded choice of flat indices on every run,
+    in index order, so that two builds can be compared element for element."""
+    os.makedirs(d, exist_ok=True)
+    left = limit - 1024 * len(arrays)  # (room for the .npy headers)
+    items = sorted(arrays.items(), key=lambda kv: np.asarray(kv[1]).nbytes)
+    for i, (name, a) in enumerate(items):
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        share = left // (len(items) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def run_cfg1(args, ctx):
     from neuralplda_amd import _lib, ops
     dev, rank, world = ctx.dev, ctx.rank, ctx.world
@@ -333,6 +379,7 @@ def run_cfg1(args, ctx):
         return ops.score_pairs(x1, x2, packed)
 
     elapsed, kern_ms, s = timed_steps(ctx, step, args.steps, args.warmup)
+    kept = keep_outputs(args, scores=s)
     checksum = float(s.double().sum().item())
     if not np.isfinite(checksum):
         raise SystemExit("non-finite scores")
@@ -340,14 +387,14 @@ def run_cfg1(args, ctx):
     # Untimed extra pass: the shader clock the chip holds under this kernel.  A one-wave probe (nplda_clock_probe) sits
     # on a side stream next to 12 more launches and compares the shader-cycle counter with the constant 100 MHz counter.
     sclk_mhz = None
-    if rank == 0 and not args.no_clock_probe and not ctx.emulated:
+    if rank == 0 and args.full and not args.no_clock_probe and not ctx.emulated:
         sclk_mhz = sclk_under(ctx, step, kern_ms)
 
     # Untimed: the cold start.  After one second of idle the clock has ramped down; the first launches run at about half
     # speed (a single 1 M-pair scoring call from an idle GPU takes roughly twice the steady-state time).  Ten back-to-back
     # launches, each bracketed by its own events.
     after_idle = None
-    if rank == 0 and world == 1 and not ctx.emulated and not args.no_alt:
+    if rank == 0 and world == 1 and args.full and not ctx.emulated and not args.no_alt:
         torch.cuda.synchronize()
         time.sleep(1.0)
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
@@ -359,7 +406,7 @@ def run_cfg1(args, ctx):
         after_idle = [round(a.elapsed_time(b), 4) for a, b in evs]
 
     alt = alt170 = None
-    if rank == 0 and args.precision == "fp32" and not args.no_alt and not ctx.emulated:
+    if rank == 0 and args.full and args.precision == "fp32" and not args.no_alt and not ctx.emulated:
         # the opt-in split-bf16 scoring kernel on the same inputs (reported beside, never as `value`)
         pk3 = ops.pack_params(*params, precision="bf16x3")
         ms3, s3 = kernel_ms_of(lambda: ops.score_pairs(x1, x2, pk3))
@@ -438,8 +485,10 @@ def run_cfg1(args, ctx):
         out["alt_bf16x3"] = alt
     if alt170 is not None:
         out["alt_d170"] = alt170
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(sorted({D, 170}), D0, D, args.cpu_seconds)
+    if kept is not None:
+        out["_outputs"] = kept
     return out
 
 
@@ -521,6 +570,7 @@ def run_cfg3(args, ctx):
         return out
 
     elapsed, step_ms, out = timed_steps(ctx, step, args.steps, args.warmup)
+    kept = keep_outputs(args, normalized_scores=out)
     # phase times: three extra synchronised passes after the timed region (the phase events are reused per step)
     phase_events["on"] = True
     for _ in range(3):
@@ -574,7 +624,7 @@ def run_cfg3(args, ctx):
              6 * 2.0 * (32 * ((nb_ + 1) // 2)) * rows_local * M / (stats_ms * 1e-3) / 1e12, "bf16_dense_peak_TFLOPs": 2500.0} \
         if split_form else {"arith": "fp32-input MFMA"}
     arith["frac_bf16_issued"] = arith["bf16_issued_TFLOPs"] / 2500.0 if split_form else None
-    return {
+    line = {
         "metric": "AS-normalised trials/sec (10k-utterance cohort, top-500)",
         "value": (thi - tlo if ctx.emulated else T) * args.steps / elapsed,
         "unit": "trials/s",
@@ -613,6 +663,9 @@ def run_cfg3(args, ctx):
                                  **({"stats_ms_prepared_cohort": stats_prepared_ms} if stats_prepared_ms is not None else {})},
                                 sclk),
     }
+    if kept is not None:
+        line["_outputs"] = kept
+    return line
 
 
 def run_cfg2(args, ctx):
@@ -699,6 +752,7 @@ def run_cfg2(args, ctx):
 
     elapsed, step_ms, loss = timed_steps(ctx, step, args.steps, args.warmup, per_step_events=False, settle_s=0.08,
                                          step_many=step_many if by_cursor else None)
+    kept = keep_outputs(args, loss=loss, **dict(zip(PARAM_NAMES, model._params())))
     if not torch.isfinite(loss).all():
         raise SystemExit("non-finite training loss")
     sclk = None
@@ -710,7 +764,7 @@ def run_cfg2(args, ctx):
     fwd = 2 * (2 * D0 * D + 2 * D * D) + 8 * D
     flops = 2 * fwd + 2 * (2 * D * D)
     achieved = Bl * flops / (step_ms * 1e-3) / 1e12
-    return {
+    line = {
         "metric": "trained trial-pairs/sec (4096-pair minibatches, SoftCdet + backward + Adam)",
         "value": (Bl if ctx.emulated else Bg) * args.steps / elapsed,
         "unit": "pairs/s",
@@ -744,6 +798,9 @@ def run_cfg2(args, ctx):
                                            " (forward + loss + data gradients, weight-gradient slabs, update), whole step",
                                  "kernel_ms": step_ms, "flop_per_pair_algorithmic": flops}, sclk),
     }
+    if kept is not None:
+        line["_outputs"] = kept
+    return line
 
 
 def _traffic(key):
@@ -808,6 +865,7 @@ def run_cfg5(args, ctx):
     _, copy_ms, _ = timed_steps(ctx, step_copy, max(args.steps // 2, 10), args.warmup, per_step_events=False, settle_s=0.08)
     elapsed, step_ms, out = timed_steps(ctx, step, args.steps, args.warmup, per_step_events=False, settle_s=0.02)
     loss, dx1, dx2 = out
+    kept = keep_outputs(args, loss=loss, dx1=dx1, dx2=dx2, **dict(zip(PARAM_NAMES, model._params())))
     if not (torch.isfinite(loss).all() and torch.isfinite(dx1.float()).all() and torch.isfinite(dx2.float()).all()):
         raise SystemExit("non-finite loss / input gradient")
     sclk = None
@@ -818,7 +876,7 @@ def run_cfg5(args, ctx):
     fwd = 2 * (2 * D0 * D + 2 * D * D) + 8 * D
     flops = 2 * fwd + 2 * (2 * D * D) + 2 * (2 * D0 * D)  # cfg2's step + the dx = du . W1 GEMM of both sides
     achieved = B * flops / (step_ms * 1e-3) / 1e12
-    return {
+    line = {
         "metric": "fine-tuned trial-pairs/sec through the NPLDA head (bf16 x-vectors in, dL/dx out, SoftCdet + Adam)",
         "value": (B if ctx.emulated else B * world) * args.steps / elapsed, "unit": "pairs/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup,
@@ -844,6 +902,9 @@ def run_cfg5(args, ctx):
                                  "frac": achieved / FP32_MFMA_PEAK_TFLOPS, "traffic": _traffic(f"head_step_dx_D{D}_B{B}"),
                                  "kernel": step_fn.describe(), "kernel_ms": step_ms, "flop_per_pair_algorithmic": flops}, sclk),
     }
+    if kept is not None:
+        line["_outputs"] = kept
+    return line
 
 
 def run_dropin(args, ctx, B=4096, n_utt=200000, n_valid=1 << 20):
@@ -1209,14 +1270,16 @@ def detail_path():
     return os.path.join(d, "bench_detail.json")
 
 
-def emit(out):
-    """Write the full objects to bench_detail.json and print the slim line (see above)."""
-    try:
-        with open(detail_path(), "w") as f:
-            json.dump(out, f, indent=1)
-        det = os.path.relpath(detail_path(), ROOT)
-    except OSError as e:
-        det = f"not written: {e}"
+def emit(out, detail=True):
+    """Write the full objects to bench_detail.json (`detail`) and print the slim line (see above)."""
+    det = None
+    if detail:
+        try:
+            with open(detail_path(), "w") as f:
+                json.dump(out, f, indent=1)
+            det = os.path.relpath(detail_path(), ROOT)
+        except OSError as e:
+            det = f"not written: {e}"
     def assemble(cut):
         line = {}
         for k, v in out.items():
@@ -1225,7 +1288,8 @@ def emit(out):
             line[k] = _slim(v, cut)
             if k == "config" and isinstance(v.get("workload"), str):
                 line[k]["workload"] = v["workload"]  # the contract's own description of the workload stays whole
-        line["detail"] = det
+        if det is not None:
+            line["detail"] = det
         for k in _LAST_KEYS:
             if k in out:
                 line[k] = _slim(out[k], cut)
@@ -1313,6 +1377,7 @@ def multi_rank_alts(args, ctx, out):
     def sub(**kw):
         a2 = argparse.Namespace(**vars(args))
         a2.no_alt, a2.no_clock_probe, a2.no_cpu_baseline, a2.scaling = True, True, True, "weak"
+        a2.dump_outputs = None
         for k, v in kw.items():
             setattr(a2, k, v)
         return a2
@@ -1398,9 +1463,16 @@ def main():
     ap.add_argument("--no-clock-probe", action="store_true",
                     help="skip the shader-clock probe pass (use under rocprofv3: the profiler serialises kernels)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="wall budget of the CPU baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="cfg1: also everything beside the headline that takes runs of its own (clock probe, cold start, "
+                         "alt_*, cpu_baseline, the other configs; the collective workloads at N > 1) and bench_detail.json")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path returned in its last timed step as DIR/<name>.npy (<= 64 MB in all)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.dump_outputs and args.workload in ("secondary", "dropin"):
+        raise SystemExit(f"--dump-outputs: --workload {args.workload} has no timed path of its own")
 
     emu = None
     if args.emulate_rank is not None:
@@ -1457,22 +1529,23 @@ def main():
         emit(out)
         return
     out = {"cfg1": run_cfg1, "cfg2": run_cfg2, "cfg3": run_cfg3, "cfg5": run_cfg5}[args.workload](args, ctx)
+    outputs = out.pop("_outputs", None) if out is not None else None
     if emu is not None:
         out["n_gpus"] = 1
         out["config"]["emulated_rank"] = f"{emu[0]}/{emu[1]}"
         out["config"]["note"] = ("single-GPU shard timing: this process ran rank %d's share of a %d-rank job, collectives "
                                  "replaced by their byte counts; NOT a scaling measurement" % emu)
         out.pop("cpu_baseline", None)
-    elif (rank == 0 and world == 1 and args.workload == "cfg1" and not args.no_alt and args.precision == "fp32"
+    elif (rank == 0 and world == 1 and args.full and args.workload == "cfg1" and not args.no_alt and args.precision == "fp32"
           and args.dim == 150 and args.pairs == 1 << 20):
-        # the other BASELINE configs on the driver's default line (a few hundred steps each, ~2 s in all)
+        # --full: the other BASELINE configs on the same line (a few hundred steps each, ~2 s in all)
         torch.cuda.empty_cache()
         for name, fn, kw in (("alt_cfg2", run_cfg2, {"steps": 300, "warmup": 30}), ("alt_cfg3", run_cfg3, {"steps": 20, "warmup": 3}),
                              ("alt_cfg5", run_cfg5, {"steps": 300, "warmup": 30})):
             a2 = argparse.Namespace(**vars(args))
             for k, v in kw.items():
                 setattr(a2, k, v)
-            a2.scaling = "weak"
+            a2.scaling, a2.dump_outputs = "weak", None
             try:
                 out[name] = _compact(fn(a2, ctx))
                 # the same workload at the reference's shipped shape (512 -> 170 -> 170: every conf/*.cfg)
@@ -1503,7 +1576,8 @@ def main():
         except Exception as e:
             out["alt_secondary_error"] = f"{type(e).__name__}: {e}"
         torch.cuda.empty_cache()
-    elif (world > 1 and args.workload == "cfg1" and not args.no_alt and args.precision == "fp32" and args.scaling == "weak"):
+    elif (world > 1 and args.full and args.workload == "cfg1" and not args.no_alt and args.precision == "fp32"
+          and args.scaling == "weak"):
         if rank != 0:
             out = {"config": {}}
         try:
@@ -1518,10 +1592,13 @@ def main():
             sys.stderr.write(f"bench.py rank {rank}: multi-rank alt workloads failed: {type(e).__name__}: {e}\n")
             sys.stderr.flush()
             os._exit(_alt_fail_rc())
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
     if rank == 0 or emu is not None:
         out["config"]["ranks_in_group"] = ctx.dist.get_world_size() if ctx.dist is not None else 1
         out["lib"] = _lib.build_info()
-        emit(out)
+        # (a plain line is small and whole: the detail file is for --full, or when NPLDA_BENCH_DETAIL asks for it)
+        emit(out, detail=args.full or bool(os.environ.get("NPLDA_BENCH_DETAIL")))
     if ctx.dist is not None:
         ctx.dist.destroy_process_group()
 

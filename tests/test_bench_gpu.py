@@ -43,7 +43,7 @@ def _check(line, steps, warmup, with_cpu):
 
 def test_bench_single_process_contract(hip_lib):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1",
-                          "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--cpu-seconds", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1  # exactly one JSON line
@@ -78,11 +78,44 @@ def test_bench_single_process_contract(hip_lib):
 from tests.test_bench_line_cpu import test_line_fits_the_driver_tail  # noqa: E402,F401  (also run on the GPU box)
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(hip_lib, tmp_path):
+    """Without --full the run is set-up, warm-up, exactly K timed steps, the outputs and the line: no alt objects, no CPU
+    baseline, no clock probe, no detail file.  --dump-outputs writes the scores of the last timed step, and they are the
+    scores of the seeded inputs (regenerated here as bench.py draws them) against the fp64 oracle."""
+    import importlib.util
+    import torch
+    from oracle import nplda_oracle as orc
+    B = 65536
+    out, lines = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--pairs", str(B), "--dump-outputs", str(tmp_path)],
+                      env={"NPLDA_BENCH_DETAIL": ""})
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "scored trial-pairs/sec (512-d xvec)" and d["unit"] == "pairs/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["steps"] == 3 and d["warmup"] == 1 and d["config"]["pairs_per_gpu_per_step"] == B
+    assert abs(d["value"] - B / (d["ms_per_step"] * 1e-3)) <= 1e-5 * d["value"]
+    assert not [k for k in d if k.startswith("alt_") or k in ("cpu_baseline", "first_call_ms", "detail")], list(d)
+    assert "sclk_mhz_under_kernel" not in d["roofline"] and 0 < d["roofline"]["kernel_ms"] <= d["ms_per_step"] * 1.02
+    assert sorted(os.listdir(tmp_path)) == ["scores.npy"]
+    s = np.load(tmp_path / "scores.npy")
+    assert s.dtype == np.float32 and s.shape == (B,) and np.isfinite(s).all()
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    prm, _ = b.make_params(150, "cpu")
+    p = orc.Params(*[t.numpy() for t in prm])
+    gen = torch.Generator(device="cuda").manual_seed(1234)
+    x1 = torch.randn(B, 512, device="cuda", generator=gen)
+    x2 = torch.randn(B, 512, device="cuda", generator=gen)
+    ref = orc.forward(x1[-512:].cpu().numpy(), x2[-512:].cpu().numpy(), p, np.float64)
+    assert np.all(np.abs(s[-512:] - ref) <= 2e-5 + 1e-5 * np.abs(ref)), np.abs(s[-512:] - ref).max()
+
+
 def test_bench_torchrun_one_rank(hip_lib):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", "29533", os.path.join(ROOT, "bench.py"),
-                          "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-alt"],
+                          "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-alt", "--full"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -214,7 +247,7 @@ def test_driver_scale_command_carries_the_collective_workloads(hip_lib):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", NPLDA_BENCH_BACKEND="gloo")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", "29541", os.path.join(ROOT, "bench.py"),
-                          "--gpus", "2", "--steps", "3", "--warmup", "1"],
+                          "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -246,7 +279,7 @@ def test_scale_command_watchdog_keeps_the_headline(hip_lib):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", NPLDA_BENCH_BACKEND="gloo", NPLDA_BENCH_ALT_SECONDS="0.2")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", "29543", os.path.join(ROOT, "bench.py"),
-                          "--gpus", "2", "--steps", "3", "--warmup", "1"],
+                          "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -38,3 +38,42 @@ def test_line_fits_the_driver_tail():
     assert d["alt_cfg3"]["stats_ms"] > 0 and d["alt_cfg3"]["allgather_bytes"] == 704000
     assert d["roofline"]["frac"] == pytest.approx(big["roofline"]["frac"], rel=1e-6) and d["cpu_baseline"]["cores"] >= 1
     assert d["config"]["workload"] == big["config"]["workload"] and d["metric"] == big["metric"]
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
+def test_dump_outputs_writer_caps_and_samples(tmp_path):
+    """bench.write_outputs (--dump-outputs): float32 / float64 .npy files, within the byte limit, small arrays whole, a
+    large one as the same seeded sample of its elements in index order on every run."""
+    import numpy as np
+    b = _bench_module()
+    arrays = {"loss": np.array([1.5], np.float32), "scores": np.arange(1 << 16, dtype=np.float64),
+              "dx": np.arange(4096, dtype=np.int32).reshape(64, 64)}
+    limit = 96 * 1024
+    for d in (tmp_path / "a", tmp_path / "b"):
+        b.write_outputs(str(d), arrays, limit=limit)
+    got = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["dx.npy", "loss.npy", "scores.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in got) <= limit
+    assert got["loss.npy"].dtype == np.float32 and got["loss.npy"].tolist() == [1.5]
+    assert got["dx.npy"].dtype == np.float32 and np.array_equal(got["dx.npy"], arrays["dx"])
+    s = got["scores.npy"]
+    assert s.dtype == np.float64 and 0 < s.size < arrays["scores"].size and np.all(np.diff(s) > 0)
+    for f in got:
+        assert np.array_equal(got[f], np.load(tmp_path / "b" / f))
+
+
+def test_bench_options():
+    """--full (everything beside the headline) and --dump-outputs DIR are bench.py options."""
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                         timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert "--full" in out.stdout and "--dump-outputs DIR" in out.stdout

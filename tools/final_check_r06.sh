@@ -5,7 +5,7 @@ TAG=${1:-r06fin4}; R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/$TAG; mkdir -p 
 ( time python -m pytest tests -m gpu -x -q > $O/gputests.txt 2>&1 ) 2>&1 | grep real
 tail -1 $O/gputests.txt
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $O/smoke.txt
-( time python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err ) 2>&1 | grep real
+( time python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err ) 2>&1 | grep real
 cp gpurun_out/bench_detail.json $O/bench_detail.json
 python bench.py --workload cfg3 > $O/bench_cfg3.json 2> $O/bench_cfg3.err
 python bench.py --workload cfg3 --dim 170 > $O/bench_cfg3_d170.json 2>> $O/bench_cfg3.err
