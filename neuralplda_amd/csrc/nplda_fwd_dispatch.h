@@ -1,6 +1,7 @@
 // nplda_fwd_dispatch.h — host-side selection of the forward kernel variant (shared by the .hip files).
 #pragma once
 #include <cstdlib>
+#include <cstring>
 #include "nplda_fwd_kernel.h"
 #include "nplda_fwd_small.h"
 #include "nplda_fwd_v2.h"
@@ -98,6 +99,12 @@ static inline int launch_fwd_v5(FwdArgs a, const NpldaLayout& L, hipStream_t st)
 // pair scoring at D1 = D2 = 150 (the headline shape): nine full blocks on the 16 x 16 MFMA, the six left-over features on
 // 4 x 4 x 1 MFMAs (nplda_fwd_v6.h) — 0.842 against v3's 0.831 of the fp32 MFMA peak at 1 M pairs
 static inline bool fwd_v6_ok(const NpldaLayout& L) { return L.NB == 10 && L.D1 == 150 && L.D2 == 150; }
+// layer 2 of v6: split form (three bf16 pieces, six 16x16x32 passes) by default; NPLDA_FWD_V6_L2=f32 selects the fp32 form
+// (A/B measurements only)
+static inline bool fwd_v6_l2_f32() {
+    static const bool f32 = getenv("NPLDA_FWD_V6_L2") != nullptr && strcmp(getenv("NPLDA_FWD_V6_L2"), "f32") == 0;
+    return f32;
+}
 template <int XM = 0>
 static inline int launch_fwd_v6(FwdArgs a, const NpldaLayout& L, hipStream_t st) {
     constexpr int WAVES = 8;
@@ -111,7 +118,12 @@ static inline int launch_fwd_v6(FwdArgs a, const NpldaLayout& L, hipStream_t st)
     const long long blocks = ntiles < cus ? ntiles : cus;
     // (2 k16-steps per fence, layer-1 MFMA groups of 5 + 4 blocks, layer-2 output groups of 3: the best of tools/exp_fwd.hip's
     // sweep, profiles/r05x_exp_v6_groups.txt)
-    hipLaunchKernelGGL((nplda_fwd_v6_kernel<10, 6, WAVES, 2, 5, 3, XM>), dim3((unsigned)blocks), dim3(WAVES * 64), 0, st, a, (int)ntiles);
+    if (fwd_v6_l2_f32())
+        hipLaunchKernelGGL((nplda_fwd_v6_kernel<10, 6, WAVES, 2, 5, 3, XM, 0, 2, 0>), dim3((unsigned)blocks), dim3(WAVES * 64), 0, st, a,
+                           (int)ntiles);
+    else
+        hipLaunchKernelGGL((nplda_fwd_v6_kernel<10, 6, WAVES, 2, 5, 3, XM, 0, 2, 1>), dim3((unsigned)blocks), dim3(WAVES * 64), 0, st, a,
+                           (int)ntiles);
     return nplda_launch_status();
 }
 // the streaming pair kernel of a model: v6 at 150 / 150, v3 up to NB = 10 otherwise, v5 at NB = 11 / 12
@@ -299,7 +311,10 @@ static inline const char* pair_kernel_name(long long n, const NpldaLayout& L) {
         case FWD_MID: return "nplda_fwd_mid_kernel (balanced 16-pair tiles, K-split layer 1, groups of 2 tiles)";
         default:
             if (fwd_v6_ok(L) && !(getenv("NPLDA_FWD_NO_V6") != nullptr && getenv("NPLDA_FWD_NO_V6")[0] == '1'))
-                return "nplda_fwd_v6_kernel (persistent, 9 feature blocks on 16x16x4 MFMAs + 6 features on 4x4x1 MFMAs)";
+                return fwd_v6_l2_f32()
+                           ? "nplda_fwd_v6_kernel (persistent, 9 feature blocks on 16x16x4 MFMAs + 6 features on 4x4x1 MFMAs)"
+                           : "nplda_fwd_v6_kernel (persistent, layer 1: 9 feature blocks on 16x16x4 MFMAs + 6 features on 4x4x1 "
+                             "MFMAs; layer 2: split bf16x3, 6 passes of 16x16x32)";
             return L.NB <= 10 ? "nplda_fwd_v3_kernel (persistent, 8 waves x 16 pairs, weights through LDS)"
                               : "nplda_fwd_v5_kernel (persistent, LDS-DMA weight chunks, layer 2 by output groups)";
     }

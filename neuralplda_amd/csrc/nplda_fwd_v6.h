@@ -27,13 +27,26 @@
 // (tools/exp_valu_phase.hip, profiles/r05u_exp_valu_phase.txt), and hipcc unpacks v_pk_fma_f32 it finds in an MFMA's
 // shadow.  With no tail work at all the kernel runs in 2.91 ms (ABL = 1): 0.12 ms is what six features cost at the full
 // blocks' rate, 0.18 ms is what they cost here.  At D = 170 (ten tail features, three quads) the form is behind v5.
+//
+// Layer 2 in split form (L2S = 1, the default of the dispatch): the normalised y and W2 each become three bf16 pieces
+// (nplda_fwd_bf16x3.h, split3x8) and every product is six v_mfma_f32_16x16x32_bf16 passes with fp32 accumulation — the
+// products of the fp32 form to fp32 rounding, at 16 cycles per 16 x 16 x 32 where the fp32 form takes 8 x 32 cycles.  All NB
+// output blocks (the tail block included: its padded rows are zero in the image and in b2 / Q / P) are live across the NB / 2
+// k32-steps; step c takes accumulator blocks 2 c and 2 c + 1 as its B operand, split just in time.  The fp32 image already
+// holds the A operand: W2p[2 c][nb][lane] and W2p[2 c + 1][nb][lane] are the eight values k(e) of lane (j, g) that the bf16
+// image of nplda_fwd_bf16x3.h packs.  The block splits each k32-step of W2 ONCE: 64-lane units (output block nb) are spread
+// over the waves, loaded from global memory into registers a step ahead, split and stored as bf16 pieces into one of two
+// LDS buffers [nb][piece][lane] between the MFMAs of the step before (1 / WAVES of the split per wave; no derived image in
+// the packed buffer, which training rewrites in place).  L2S = 0: the fp32 layer 2 below (NPLDA_FWD_V6_L2=f32, A/B only).
 #pragma once
 #include "nplda_fwd_kernel.h"
+#include "nplda_fwd_bf16x3.h"
 
 namespace nplda {
 
 // ABL (tools/exp_fwd.hip only; results are WRONG when non-zero): 1 = no tail work at all
-template <int NB, int TF, int WAVES, int KPB = 2, int G1 = 5, int G2 = 3, int XM = 0, int ABL = 0, int NCH = 2>  // NCH: accumulator chains per (quad, side)
+template <int NB, int TF, int WAVES, int KPB = 2, int G1 = 5, int G2 = 3, int XM = 0, int ABL = 0, int NCH = 2,  // NCH: accumulator chains per (quad, side)
+          int L2S = 0>                                                                                            // L2S: layer 2 in split form
 __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void nplda_fwd_v6_kernel(const FwdArgs a, int ntiles) {
     constexpr int NM = NB - 1;                       // feature blocks on the 16 x 16 MFMA
     constexpr int NQ = (TF + 3) / 4;                 // tail features in quads
@@ -43,10 +56,14 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void nplda_fwd_v6_kernel(con
     constexpr int NGR = (NM + G1 - 1) / G1;          // MFMA groups of a layer-1 step; tail quad q rides with group q
     constexpr int NG = (NM + G2 - 1) / G2;           // layer-2 output groups; tail quad q rides with group q
     constexpr int NSEG2 = NB * (G2 + 1);             // a group's chunk: NB k-blocks x (its blocks + the tail block)
-    constexpr int CH2 = NSEG2 * 64;
+    constexpr int CH2 = L2S ? 0 : NSEG2 * 64;        // (split form: layer 2 does not use wbuf)
     constexpr int CH = CH1 > CH2 ? CH1 : CH2;
+    constexpr int KC2 = NB / 2;                      // split form: k32-steps of layer 2
     static_assert(TF >= 1 && TF <= 16 && NM >= 1 && NQ <= NGR && NQ <= NG, "tail quads ride with the MFMA groups");
+    static_assert(!L2S || (NB % 2 == 0 && WAVES <= NB && NB <= 2 * WAVES), "split layer 2: k32-steps of two whole accumulator "
+                                                                            "blocks, one or two W2 units per wave");
     __shared__ f32x4 wbuf[2][CH];
+    __shared__ bf16x8 wsp[L2S ? 2 : 1][L2S ? NB * 3 * 64 : 1];  // split form: W2 pieces of one k32-step, [nb][piece][lane]
     __shared__ f32x4 cvec[4][NB * 4];
     __shared__ f32x4 sink[64];
 
@@ -107,6 +124,29 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void nplda_fwd_v6_kernel(con
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
     };
+    // split form: W2 units of k32-step c — unit i of this wave is output block wave + WAVES i (i < 2); register slot r holds
+    // one unit between its load and its split.  Loads are unconditional (a unit past NB re-reads block 0), the split and
+    // the stores of such a unit are skipped (a scalar branch: `two` is wave-uniform)
+    f32x4 w2lo[2], w2hi[2];
+    const bool two = wave + WAVES < NB;
+    // (a wave-uniform base and an opaque 32-bit lane offset: with plain indexing hipcc hoists a 64-bit address per load out
+    // of the tile loop — twenty register pairs, and the kernel spills)
+    auto w2_load = [&](int c, int i, int r) {
+        const int nb = wave + WAVES * i;
+        const char* base = reinterpret_cast<const char*>(Wall + w2base4 + (long long)(2 * c) * STEP4 + (nb < NB ? nb : 0) * 64);
+        unsigned lo = (unsigned)lane * 16u;
+        asm volatile("" : "+v"(lo));
+        w2lo[r] = *reinterpret_cast<const f32x4*>(base + lo);
+        w2hi[r] = *reinterpret_cast<const f32x4*>(base + STEP4 * 16 + lo);
+    };
+    auto w2_store = [&](int i, int r, bf16x8* dst) {
+        const int nb = wave + WAVES * i;
+        bf16x8 h, m, l;
+        split3x8(w2lo[r], w2hi[r], h, m, l);
+        dst[(nb * 3 + 0) * 64 + lane] = h;
+        dst[(nb * 3 + 1) * 64 + lane] = m;
+        dst[(nb * 3 + 2) * 64 + lane] = l;
+    };
     // the four k-groups' partial sums of one tail feature -> the full sum in every lane of the row
     auto kgroups_sum = [&](float v) {
         v = wave_xor_add(v, 16);
@@ -128,13 +168,21 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void nplda_fwd_v6_kernel(con
         t0 = (t * WAVES + wave) * 16;
         r = t0 + j;
     };
+    // row pointers of a tile (the split form recomputes the next tile's where it needs them: two 64-bit pointers per lane
+    // kept across layer 2 would not fit beside its live accumulators)
+    auto tile_ptrs = [&](long long t, long long& t0, bool& ok, const float*& pa, const float*& pb) {
+        long long r;
+        tile_rows(t, t0, r);
+        ok = r < a.n;
+        if (!ok) r = a.n - 1;
+        pa = x_row<XM>(a.xa, r, a.ldx);
+        pb = x_row<XM>(a.xb, r, a.ldx);
+    };
     long long tile = blockIdx.x;
-    long long t0, row;
-    tile_rows(tile, t0, row);
-    bool ok = row < a.n;
-    if (!ok) row = a.n - 1;
-    const float* sa = x_row<XM>(a.xa, row, a.ldx);
-    const float* sb = x_row<XM>(a.xb, row, a.ldx);
+    long long t0;
+    bool ok;
+    const float *sa, *sb;
+    tile_ptrs(tile, t0, ok, sa, sb);
 
     dma_l1(0, wbuf[0]);
     f32x4 xa[KPB], xb[KPB];
@@ -149,12 +197,10 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void nplda_fwd_v6_kernel(con
 
     for (;;) {
         const long long tile_n = tile + gridDim.x;
-        long long t0_n, row_n;
-        tile_rows(tile_n, t0_n, row_n);
-        const bool ok_n = row_n < a.n;
-        if (!ok_n) row_n = a.n - 1;
-        const float* sa_n = x_row<XM>(a.xa, row_n, a.ldx);
-        const float* sb_n = x_row<XM>(a.xb, row_n, a.ldx);
+        long long t0_n;
+        bool ok_n;
+        const float *sa_n, *sb_n;
+        tile_ptrs(tile_n, t0_n, ok_n, sa_n, sb_n);
 
         f32x4 accA[NB], accB[NB];
 #pragma unroll
@@ -182,6 +228,10 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void nplda_fwd_v6_kernel(con
             const bool more = (c + 1 < NC1);
             f32x4* nxt = wbuf[par ^ 1];
             if (more) dma_l1(c + 1, nxt);
+            else if constexpr (L2S) {
+                w2_load(0, 0, 0);
+                w2_load(0, 1, 1);
+            }
             else dma_l2(0, (G2 < NM ? G2 : NM), nxt);
 #pragma unroll
             for (int s = 0; s < KPB; ++s) {
@@ -219,6 +269,12 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void nplda_fwd_v6_kernel(con
                             }
                         }
                     }
+                }
+            }
+            if constexpr (L2S) {
+                if (!more) {
+                    w2_store(0, 0, wsp[0]);
+                    if (two) w2_store(1, 1, wsp[0]);
                 }
             }
             chunk_fence();
@@ -280,8 +336,67 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void nplda_fwd_v6_kernel(con
             }
         }
 
-        // ---- layer 2, output groups of G2 full blocks (+ tail quad gi); the score is folded group by group --------------
         float part = 0.f;
+        if constexpr (L2S) {
+        // ---- layer 2 in split form: k32-step c takes accumulator blocks 2 c and 2 c + 1, all NB output blocks live --------
+            f32x4 zA[NB], zB[NB];
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) {
+                zA[nb] = b2p[4 * nb + g];
+                zB[nb] = zA[nb];
+            }
+#pragma unroll
+            for (int c = 0; c < KC2; ++c) {
+                const bool more = c + 1 < KC2;
+                if (more) {
+                    w2_load(c + 1, 0, 0);
+                } else {
+                    dma_l1(0, wbuf[par]);  // chunk 0 of the next tile (both layer-1 buffers are free here), and its first x rows
+                    long long t0_x;
+                    bool ok_x;
+                    const float *pa, *pb;
+                    tile_ptrs(tile_n, t0_x, ok_x, pa, pb);
+#pragma unroll
+                    for (int s = 0; s < KPB; ++s) {
+                        xa[s] = load_xrow<XM>(pa, 16 * s + 4 * g, D0);
+                        xb[s] = load_xrow<XM>(pb, 16 * s + 4 * g, D0);
+                    }
+                }
+                bf16x8 ah, am, al, bh, bm, bl;
+                split3x8(accA[2 * c], accA[2 * c + 1], ah, am, al);
+                split3x8(accB[2 * c], accB[2 * c + 1], bh, bm, bl);
+                const bf16x8* w = wsp[c & 1];
+#pragma unroll
+                for (int nb = 0; nb < NB; nb += 2) {
+                    WFrag w0, w1;
+                    w0.h = w[(nb * 3 + 0) * 64 + lane];
+                    w0.m = w[(nb * 3 + 1) * 64 + lane];
+                    w0.l = w[(nb * 3 + 2) * 64 + lane];
+                    w1.h = w[(nb * 3 + 3) * 64 + lane];
+                    w1.m = w[(nb * 3 + 4) * 64 + lane];
+                    w1.l = w[(nb * 3 + 5) * 64 + lane];
+                    mfma6x4(w0, w1, ah, am, al, bh, bm, bl, zA[nb], zB[nb], zA[nb + 1], zB[nb + 1]);
+                    if (more && nb == 2 * ((NB / 2) / 2)) {  // past the middle: unit 0 has landed; unit 1 reuses its registers
+                        w2_store(0, 0, wsp[(c + 1) & 1]);
+                        w2_load(c + 1, 1, 0);
+                    }
+                }
+                if (more && two) w2_store(1, 0, wsp[(c + 1) & 1]);
+                chunk_fence();
+            }
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) {
+                const f32x4 q = Qp[4 * nb + g];
+                const f32x4 p = Pp[4 * nb + g];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float z1 = zA[nb][r], z2 = zB[nb][r];
+                    part = fmaf(q[r], fmaf(z1, z1, z2 * z2), part);
+                    part = fmaf(2.0f * p[r], z1 * z2, part);
+                }
+            }
+        } else {
+        // ---- layer 2, output groups of G2 full blocks (+ tail quad gi); the score is folded group by group --------------
 #pragma unroll
         for (int gi = 0; gi < NG; ++gi) {
             const int nb0 = gi * G2;
@@ -368,14 +483,19 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void nplda_fwd_v6_kernel(con
                 part += (g == 0) ? tpart : 0.f;
             }
         }
+        }  // fp32 layer 2
         part = wave_xor_add(part, 16);
         part = wave_xor_add(part, 32);
         if (g == 0 && ok) a.out_s[t0 + j] = part;
 
         tile = tile_n;
         if (tile >= ntiles) break;
-        t0 = t0_n; ok = ok_n;
-        sa = sa_n; sb = sb_n;
+        if constexpr (L2S) {
+            tile_ptrs(tile, t0, ok, sa, sb);
+        } else {
+            t0 = t0_n; ok = ok_n;
+            sa = sa_n; sb = sb_n;
+        }
     }
 }
 
