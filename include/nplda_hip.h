@@ -617,6 +617,37 @@ int nplda_score_pairs_bf16x3(const float* x1, const float* x2, int64_t B, int64_
 int nplda_embed_bf16x3(const float* x, int64_t N, int64_t ldx, const void* packed, int D0, int D1, int D2,
                        float* z, int64_t ldz, float* q, nplda_stream_t stream);
 
+/* ---- E-TDNN x-vector extractor (utils/models.py:29-214) ------------------------------------------------------ */
+
+/* XVectorNet_ETDNN_12Layer.extract (utils/models.py:170-186): MFCC frames -> 512-d x-vectors, exact fp32 MFMA
+ * (csrc/nplda_xvec.hip).  tdnn1..tdnn10 (unfold c frames at dilation d, nn.Linear, ReLU, eval-mode
+ * BatchNorm1d(affine=False)), statistics pooling [mean | unbiased std or var] over time, lin11 (affine only).
+ * An utterance of T frames yields T - 22 pooled frames; T = 23 gives NaN std / var, as the reference does. */
+#define NPLDA_XVEC_LAYOUT_ROWS 0  /* x: (total_frames, 30) rows with row stride ld_in >= 30                    */
+#define NPLDA_XVEC_LAYOUT_BCT  1  /* x: the reference's (n_utts, 30, T) contiguous, T = total_frames / n_utts  */
+#define NPLDA_XVEC_POOL_STD    0  /* pooling_function = torch.std (default)                                  */
+#define NPLDA_XVEC_POOL_VAR    1  /* pooling_function = torch.var (E2EConf pooling_function = var)           */
+
+/* Bytes of the packed extractor image (fixed architecture, 24.5 MB). */
+size_t nplda_xvec_packed_bytes(void);
+/* Pack the extractor's parameters.  W, b: HOST arrays of 11 device pointers, tdnn1..tdnn10 kernel.weight (Dout,
+ * c * Din) / kernel.bias, then lin11.weight (512, 3000) / lin11.bias; running_mean, running_var: host arrays of 10
+ * device pointers (tdnn<i>.bn); eps: host array of 10 floats.  Batch norm is folded as (mean, 1 / sqrt(var + eps)). */
+int nplda_xvec_pack_f32(const float* const* W, const float* const* b, const float* const* running_mean,
+                        const float* const* running_var, const float* eps, void* packed, size_t packed_bytes,
+                        nplda_stream_t stream);
+/* Workspace of one nplda_xvec_extract_f32 call over total_frames frames of n_utts utterances (8 KB per frame plus
+ * 12 KB per utterance, rounded to whole tiles). */
+size_t nplda_xvec_workspace_bytes(int64_t total_frames, int64_t n_utts);
+/* out[u, 0:512] = extract(utterance u) for u < n_utts.  offsets: int64 device array of n_utts + 1 frame offsets
+ * (utterance u is frames [offsets[u], offsets[u+1]), each at least 23 frames long for a finite result; for LAYOUT_BCT
+ * offsets[u] = u T).  out: (n_utts, ldx), ldx >= 512, ldx % 4 == 0.  Every layer runs over all frames in one launch; an
+ * utterance's result does not depend on the rest of the batch (bit for bit).  The caller's x is read only inside its
+ * total_frames rows. */
+int nplda_xvec_extract_f32(const float* x, int layout, int64_t ld_in, const int64_t* offsets, int64_t n_utts,
+                           int64_t total_frames, int pooling, const void* packed, float* out, int64_t ldx, void* ws,
+                           size_t ws_bytes, nplda_stream_t stream);
+
 /* ---- measurement utility ------------------------------------------------------------------------------------- */
 
 /* Shader-clock probe for bench.py (no reference counterpart): one wave that stays resident for window_us microseconds

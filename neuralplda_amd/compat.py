@@ -8,6 +8,9 @@ MI355X-native implementations:
 
     import neuralplda_amd.compat as compat; compat.install()
     model = pickle.load(open('models/NPLDA_12_1600000000.pt', 'rb'))   # -> neuralplda_amd.models.NeuralPlda
+
+`utils.models.TDNN`, `.XVectorNet_ETDNN_12Layer` and `.Etdnn_Xvec_NeuralPlda` resolve to neuralplda_amd.xvector's classes
+(models.py names them), and `utils.NpldaConf.E2EConf` to this package's E2EConf.
 """
 import sys
 import types

@@ -17,7 +17,18 @@ import torch.nn as nn
 
 from . import _lib, kaldi_format, ops
 
-__all__ = ["NeuralPlda", "GaussianBackend", "arr2val"]
+__all__ = ["NeuralPlda", "GaussianBackend", "arr2val", "TDNN", "XVectorNet_ETDNN_12Layer", "Etdnn_Xvec_NeuralPlda"]
+
+_XVECTOR_NAMES = ("TDNN", "XVectorNet_ETDNN_12Layer", "Etdnn_Xvec_NeuralPlda")
+
+
+def __getattr__(name):
+    """The extractor classes (utils/models.py:29-345) live in xvector.py, which imports this module: they are resolved
+    here on first use, so that `utils.models.Etdnn_Xvec_NeuralPlda` (compat aliases, reference pickles) names them."""
+    if name in _XVECTOR_NAMES:
+        from . import xvector
+        return getattr(xvector, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def arr2val(x, retidx):

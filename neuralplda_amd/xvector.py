@@ -1,0 +1,301 @@
+"""E-TDNN x-vector extractor and the joint model on top of it (utils/models.py:29-345).
+
+`TDNN`, `XVectorNet_ETDNN_12Layer` and `Etdnn_Xvec_NeuralPlda` keep the reference's constructors, attribute names and
+state-dict keys (so its checkpoints and whole-module pickles load), but only the extraction path computes, and it runs as
+hand-written HIP (csrc/nplda_xvec.hip through include/nplda_hip.h):
+
+    extract(x)                     (B, 30, T) features -> (B, 512) x-vectors                 (utils/models.py:170-186)
+    extract_ragged(frames, lens)   (sum T_u, 30) frames of utterances of different lengths -> (U, 512)
+    Etdnn_Xvec_NeuralPlda.forward  extract both sides, then the existing HIP NPLDA head       (utils/models.py:251-268)
+
+Batch norm runs with its running statistics only (the reference's `train1()` puts the tdnn batch norms in eval mode);
+there is no backward through the extractor: with grad mode on, a parameter of the extractor that requires grad is an
+error, and a frozen extractor (`xvector_extractor.requires_grad_(False)`) trains the head through the head's own HIP
+backward.  The classifier path (`forward`, `prestatspool`, `postpooling`) is not provided.
+"""
+import ctypes
+import pickle
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib, kaldi_format
+from .models import NeuralPlda, _compute_device
+
+__all__ = ["TDNN", "XVectorNet_ETDNN_12Layer", "Etdnn_Xvec_NeuralPlda", "LAYERS", "CONTEXT", "flops_per_frame"]
+
+# (Din, Dout, context, dilation) of tdnn1..tdnn10 (utils/models.py:104-123)
+LAYERS = ((30, 512, 5, 1), (512, 512, 1, 1), (512, 512, 3, 2), (512, 512, 1, 1), (512, 512, 3, 3), (512, 512, 1, 1),
+          (512, 512, 3, 4), (512, 512, 1, 1), (512, 512, 1, 1), (512, 1500, 1, 1))
+CONTEXT = sum(d * (c - 1) for _, _, c, d in LAYERS)  # 22 frames lost per utterance
+FEAT, XVEC_DIM, POOL_DIM = 30, 512, 1500
+LAYOUT_ROWS, LAYOUT_BCT = 0, 1  # include/nplda_hip.h NPLDA_XVEC_LAYOUT_*
+POOL_STD, POOL_VAR = 0, 1       # NPLDA_XVEC_POOL_*
+MAX_WORKSPACE_BYTES = 1 << 30   # per extraction call; larger batches are split by utterance
+
+
+def flops_per_frame():
+    """Algorithmic FLOP per frame of tdnn1..tdnn10 (2 K N each) and per utterance of lin11."""
+    frame = sum(2 * c * din * dout for din, dout, c, _ in LAYERS)
+    return frame, 2 * 2 * POOL_DIM * XVEC_DIM
+
+
+# nplda_xvec_workspace_bytes restated (csrc/nplda_xvec.hip ws_layout) so that a batch is split without a call per utterance
+def _ws_bytes(R, U):
+    a = lambda b: (b + 255) // 256 * 256  # noqa: E731
+    rows = (R + 127) // 128 * 128 + 16
+    urows = (U + 127) // 128 * 128
+    oA = a(rows * 32 * 4)
+    oB = a(oA + rows * 512 * 4)
+    oP = a(oB + rows * 1504 * 4)
+    return a(oP + urows * 3008 * 4)
+
+
+def _chunks(lengths, limit):
+    """[(u0, u1)] runs of whole utterances whose workspace stays within `limit` bytes (one utterance at least)."""
+    out, u0, R = [], 0, 0
+    for u, T in enumerate(lengths):
+        if u > u0 and _ws_bytes(R + T, u + 1 - u0) > limit:
+            out.append((u0, u))
+            u0, R = u, 0
+        R += T
+    if u0 < len(lengths):
+        out.append((u0, len(lengths)))
+    return out
+
+
+def _pool_kind(fn):
+    if fn is torch.std:
+        return POOL_STD
+    if fn is torch.var:
+        return POOL_VAR
+    raise ValueError(f"pooling_function {fn!r}: the HIP extractor implements torch.std and torch.var")
+
+
+class TDNN(nn.Module):
+    """utils/models.py:29-96: same constructor, attributes and parameters.  It computes only inside
+    XVectorNet_ETDNN_12Layer.extract, where the ten layers run as one chain of HIP GEMMs."""
+
+    def __init__(self, input_dim=23, output_dim=512, context_size=5, stride=1, dilation=1, batch_norm=True):
+        super(TDNN, self).__init__()
+        self.context_size = context_size
+        self.stride = stride
+        self.input_dim = input_dim
+        self.output_dim = output_dim
+        self.dilation = dilation
+        self.padlen = int(dilation * (context_size - 1) / 2)
+        self.kernel = nn.Linear(input_dim * context_size, output_dim)
+        self.nonlinearity = nn.ReLU()
+        self.batch_norm = batch_norm
+        if batch_norm:
+            self.bn = nn.BatchNorm1d(output_dim, affine=False)
+
+    def forward(self, x):
+        raise NotImplementedError("a single TDNN layer runs only inside XVectorNet_ETDNN_12Layer.extract (HIP)")
+
+
+class XVectorNet_ETDNN_12Layer(nn.Module):
+    """utils/models.py:98-214: the 12-layer E-TDNN x-vector network.  `extract` / `extract_ragged` run on HIP."""
+
+    def __init__(self, noclasses=13539, pooling_function=torch.std):
+        super(XVectorNet_ETDNN_12Layer, self).__init__()
+        for i, (din, dout, c, d) in enumerate(LAYERS, 1):
+            setattr(self, f"tdnn{i}", TDNN(input_dim=din, output_dim=dout, context_size=c, dilation=d))
+        self.pooling_function = pooling_function
+        self.lin11 = nn.Linear(3000, 512)
+        self.bn11 = nn.BatchNorm1d(num_features=512, affine=False)
+        self.bn12 = nn.BatchNorm1d(num_features=512, affine=False)
+        self.lin12 = nn.Linear(512, 512)
+        self.finlin = nn.Linear(512, noclasses)
+        self.smax = nn.Softmax(dim=1)
+        self._xvec_cache = {}
+
+    def __setstate__(self, state):
+        super(XVectorNet_ETDNN_12Layer, self).__setstate__(state)
+        self.__dict__["_xvec_cache"] = {}
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state["_xvec_cache"] = {}  # device buffers do not belong in a model file
+        return state
+
+    def tdnns(self):
+        return [getattr(self, f"tdnn{i}") for i in range(1, 11)]
+
+    def invalidate_packed(self):
+        """Drop the packed weight image (needed only after writes that bypass the version counters, e.g. a foreign kernel;
+        `.data` writes of LoadFromKaldi, in-place ops and optimiser steps are noticed)."""
+        self.__dict__["_xvec_cache"] = {}
+
+    def train(self, mode=True):
+        self.invalidate_packed()
+        return super(XVectorNet_ETDNN_12Layer, self).train(mode)
+
+    def forward(self, x):
+        raise NotImplementedError("the classifier path (utils/models.py:158-168) is not provided: use extract()")
+
+    # -- packed weights -------------------------------------------------------------------------
+    def _sources(self):
+        ts = self.tdnns()
+        return ([t.kernel.weight for t in ts] + [self.lin11.weight], [t.kernel.bias for t in ts] + [self.lin11.bias],
+                [t.bn.running_mean for t in ts], [t.bn.running_var for t in ts], [float(t.bn.eps) for t in ts])
+
+    def _check_mode(self, x):
+        for i, t in enumerate(self.tdnns(), 1):
+            bn = t.bn
+            if bn.training or bn.running_mean is None or bn.running_var is None:
+                raise RuntimeError(f"tdnn{i}.bn is in training mode (batch statistics): the HIP extractor implements "
+                                   "running-statistics batch norm only; call .eval() (or Etdnn_Xvec_NeuralPlda.train1())")
+        if torch.is_grad_enabled():
+            if any(p.requires_grad for p in self.parameters()):
+                raise RuntimeError("no backward through the x-vector extractor: freeze it with "
+                                   "xvector_extractor.requires_grad_(False) or extract under torch.no_grad()")
+            if x.requires_grad:
+                raise RuntimeError("no backward through the x-vector extractor: its input must not require grad")
+
+    def _packed(self, dev):
+        """The fragment-ordered weight image on `dev`, rebuilt when any source tensor is replaced or changes version.  The
+        cache holds the source tensors themselves, so a freed parameter whose address is reused cannot hit."""
+        W, b, m, v, eps = self._sources()
+        srcs = W + b + m + v
+        cache = self.__dict__.setdefault("_xvec_cache", {})
+        key = (dev, tuple(t._version for t in srcs), tuple(eps))
+        held = cache.get("srcs")
+        if (cache.get("key") == key and held is not None and len(held) == len(srcs)
+                and all(a is b_ for a, b_ in zip(held, srcs))):
+            return cache["buf"]
+        lib = _lib.load()
+        with _lib.on_device(dev):
+            dsrc = [t.detach().to(dev, torch.float32).contiguous() for t in srcs]
+            n = lib.nplda_xvec_packed_bytes()
+            buf = torch.empty(n, dtype=torch.uint8, device=dev)
+            ptrs = [(ctypes.c_void_p * len(a))(*[t.data_ptr() for t in a])
+                    for a in (dsrc[:11], dsrc[11:22], dsrc[22:32], dsrc[32:42])]
+            e = (ctypes.c_float * 10)(*eps)
+            # (the device copies die with this frame: the caching allocator reuses them in stream order, after the pack)
+            _lib.check(lib.nplda_xvec_pack_f32(*ptrs, e, buf.data_ptr(), n, _lib.current_stream(dev)),
+                       "nplda_xvec_pack_f32")
+        cache.clear()
+        cache.update(key=key, srcs=list(srcs), buf=buf)
+        return buf
+
+    # -- extraction ------------------------------------------------------------------------------
+    def _run(self, x, layout, lengths, dev, workspace_bytes):
+        """x on `dev`, float32 contiguous: (sum T, 30) for LAYOUT_ROWS, (U, 30, T) for LAYOUT_BCT."""
+        U = len(lengths)
+        out = torch.empty((U, XVEC_DIM), dtype=torch.float32, device=dev)
+        if U == 0:
+            return out
+        packed = self._packed(dev)
+        kind = _pool_kind(self.pooling_function)
+        lib = _lib.load()
+        limit = MAX_WORKSPACE_BYTES if workspace_bytes is None else int(workspace_bytes)
+        starts = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+        with _lib.on_device(dev):
+            st = _lib.current_stream(dev)
+            for u0, u1 in _chunks(lengths, limit):
+                f0, f1 = int(starts[u0]), int(starts[u1])
+                offs = torch.from_numpy(starts[u0:u1 + 1] - f0).to(dev)
+                ws_n = lib.nplda_xvec_workspace_bytes(f1 - f0, u1 - u0)
+                ws = torch.empty(ws_n, dtype=torch.uint8, device=dev)
+                src = x[f0:f1] if layout == LAYOUT_ROWS else x[u0:u1]
+                _lib.check(lib.nplda_xvec_extract_f32(src.data_ptr(), layout, FEAT, offs.data_ptr(), u1 - u0, f1 - f0, kind,
+                                                      packed.data_ptr(), out[u0:u1].data_ptr(), XVEC_DIM, ws.data_ptr(),
+                                                      ws_n, st), "nplda_xvec_extract_f32")
+        return out
+
+    def extract(self, x, workspace_bytes=None):
+        """utils/models.py:170-186: x (B, 30, T) -> (B, 512) x-vectors = lin11([mean | std] of tdnn10 ... tdnn1 (x^T)),
+        on the HIP device (CPU input is staged through it and the result returned on the input's device)."""
+        if x.dim() != 3 or x.shape[1] != FEAT:
+            raise ValueError(f"extract expects (B, {FEAT}, T) features, got {tuple(x.shape)}")
+        self._check_mode(x)
+        B, _, T = x.shape
+        if B > 0 and T <= CONTEXT:
+            raise ValueError(f"T = {T} frames is shorter than the extractor's context ({CONTEXT + 1} frames at least)")
+        dev = _compute_device(x, self.lin11.weight)
+        X = x.detach().to(dev, torch.float32).contiguous()
+        out = self._run(X, LAYOUT_BCT, [T] * B, dev, workspace_bytes)
+        return out if out.device == x.device else out.to(x.device)
+
+    def extract_ragged(self, frames, lengths, workspace_bytes=None):
+        """x-vectors of utterances of different lengths: frames (sum T_u, 30) row-major, utterance u being the next
+        lengths[u] rows; -> (len(lengths), 512).  Same values as extract() on each utterance alone, bit for bit."""
+        if frames.dim() != 2 or frames.shape[1] != FEAT:
+            raise ValueError(f"extract_ragged expects (frames, {FEAT}) rows, got {tuple(frames.shape)}")
+        lengths = [int(T) for T in (lengths.tolist() if isinstance(lengths, (torch.Tensor, np.ndarray)) else lengths)]
+        if sum(lengths) != frames.shape[0]:
+            raise ValueError(f"lengths sum to {sum(lengths)}, frames has {frames.shape[0]} rows")
+        short = [T for T in lengths if T <= CONTEXT]
+        if short:
+            raise ValueError(f"an utterance of {short[0]} frames is shorter than the extractor's context "
+                             f"({CONTEXT + 1} frames at least; the reference's unfold raises)")
+        self._check_mode(frames)
+        dev = _compute_device(frames, self.lin11.weight)
+        X = frames.detach().to(dev, torch.float32).contiguous()
+        out = self._run(X, LAYOUT_ROWS, lengths, dev, workspace_bytes)
+        return out if out.device == frames.device else out.to(frames.device)
+
+    # -- Kaldi -----------------------------------------------------------------------------------
+    def LoadFromKaldi(self, weightspath):
+        """utils/models.py:188-214: a pickle of {component: {'params' | 'bias' | 'stats-mean' | 'stats-var': ndarray}}."""
+        with open(weightspath, 'rb') as f:
+            kw = pickle.load(f)
+        sd = self.state_dict()
+
+        def put(name, arr):
+            sd[name].data.copy_(torch.from_numpy(np.asarray(arr)).float())
+
+        for i in range(1, 11):
+            put(f'tdnn{i}.kernel.weight', kw[f'tdnn{i}.affine']['params'])
+            put(f'tdnn{i}.kernel.bias', kw[f'tdnn{i}.affine']['bias'])
+            put(f'tdnn{i}.bn.running_mean', kw[f'tdnn{i}.batchnorm']['stats-mean'])
+            put(f'tdnn{i}.bn.running_var', kw[f'tdnn{i}.batchnorm']['stats-var'])
+        put('lin11.weight', kw['tdnn11.affine']['params'])
+        put('lin11.bias', kw['tdnn11.affine']['bias'])
+        put('bn11.running_mean', kw['tdnn11.batchnorm']['stats-mean'])
+        put('bn11.running_var', kw['tdnn11.batchnorm']['stats-var'])
+        put('lin12.weight', kw['tdnn12.affine']['params'])
+        put('lin12.bias', kw['tdnn12.affine']['bias'])
+        put('bn12.running_mean', kw['tdnn12.batchnorm']['stats-mean'])
+        put('bn12.running_var', kw['tdnn12.batchnorm']['stats-var'])
+        put('finlin.weight', kw['output.affine']['params'])
+        put('finlin.bias', kw['output.affine']['bias'])
+        self.invalidate_packed()
+
+
+class Etdnn_Xvec_NeuralPlda(NeuralPlda):
+    """utils/models.py:216-345: the NPLDA head on an E-TDNN extractor.  `nc` is an E2EConf (or any object with its
+    xvector_dim, layer1_LDA_dim, layer2_PLDA_spkfactor_dim, pooling_function, beta, alpha, device, loss).  The head's
+    parameters, losses, cdet, minc and SaveModel are NeuralPlda's (the same HIP kernels)."""
+
+    def __init__(self, nc):
+        super(Etdnn_Xvec_NeuralPlda, self).__init__(nc)
+        self.pooling_function = torch.var if getattr(nc, "pooling_function", "std") == 'var' else torch.std
+        self.xvector_extractor = XVectorNet_ETDNN_12Layer(pooling_function=self.pooling_function)
+        # the reference registers the extractor before the head (state-dict order of its checkpoints)
+        mods = self._modules
+        self._modules = type(mods)([("xvector_extractor", mods["xvector_extractor"])] +
+                                   [(k, v) for k, v in mods.items() if k != "xvector_extractor"])
+
+    def train1(self):
+        """utils/models.py:231-242: training mode with the tdnn batch norms on their running statistics."""
+        self.train()
+        for t in self.xvector_extractor.tdnns():
+            t.bn.training = False
+        return self
+
+    def extract_plda_embeddings(self, x):
+        """utils/models.py:244-249."""
+        return super(Etdnn_Xvec_NeuralPlda, self).extract_plda_embeddings(self.xvector_extractor.extract(x))
+
+    def forward(self, x1, x2):
+        """utils/models.py:257-261: features (B, 30, T1), (B, 30, T2) -> scores (B,)."""
+        ext = self.xvector_extractor
+        return super(Etdnn_Xvec_NeuralPlda, self).forward(ext.extract(x1), ext.extract(x2))
+
+    def LoadParamsFromKaldi(self, xvec_etdnn_pickle_file, mean_vec_file, transform_mat_file, PldaFile):
+        """utils/models.py:323-340, the Kaldi files read natively (kaldi_format) as NeuralPlda.LoadPldaParamsFromKaldi."""
+        self.xvector_extractor.LoadFromKaldi(xvec_etdnn_pickle_file)
+        kaldi_format.fold_init(self, mean_vec_file, transform_mat_file, PldaFile)
