@@ -648,6 +648,33 @@ int nplda_xvec_extract_f32(const float* x, int layout, int64_t ld_in, const int6
                            int64_t total_frames, int pooling, const void* packed, float* out, int64_t ldx, void* ws,
                            size_t ws_bytes, nplda_stream_t stream);
 
+/* Training forward and backward of the same extractor (csrc/nplda_xvec_bwd.hip), for fine-tuning it end to end under
+ * Etdnn_Xvec_NeuralPlda.train1() (utils/models.py:238-249: the tdnn batch norms on their running statistics).  Bytes of
+ * the `saved` buffer of one nplda_xvec_extract_train_f32 call: the padded input image, every tdnn layer's normalised
+ * output and ReLU-mask bytes, a per-row index and the pooled rows (about 30 KB per frame, 12 KB per utterance). */
+size_t nplda_xvec_train_saved_bytes(int64_t total_frames, int64_t n_utts);
+/* utils/models.py:170-186 as nplda_xvec_extract_f32 (same arguments; out is bit for bit the same), keeping in `saved`
+ * what nplda_xvec_backward_f32 reads.  One call covers the whole batch (no chunking). */
+int nplda_xvec_extract_train_f32(const float* x, int layout, int64_t ld_in, const int64_t* offsets, int64_t n_utts,
+                                 int64_t total_frames, int pooling, const void* packed, float* out, int64_t ldx,
+                                 void* saved, size_t saved_bytes, nplda_stream_t stream);
+/* Bytes of the transposed weight image the data gradient reads (tdnn2..tdnn10 and lin11, W per context tap transposed). */
+size_t nplda_xvec_packed_t_bytes(void);
+/* Pack it from W: the host array of 11 device pointers of nplda_xvec_pack_f32 (W[0], tdnn1, is not read). */
+int nplda_xvec_pack_t_f32(const float* const* W, void* packed_t, size_t packed_t_bytes, nplda_stream_t stream);
+/* Floats of the flat gradient: for tdnn1..tdnn10 then lin11, dW in torch layout (Dout, c * Din) followed by db (Dout). */
+size_t nplda_xvec_grad_floats(void);
+/* Workspace of one nplda_xvec_backward_f32 call (about 10 KB per frame plus the split-K partials, 40 MB at most). */
+size_t nplda_xvec_backward_workspace_bytes(int64_t total_frames, int64_t n_utts);
+/* The autograd backward of utils/models.py:170-186 (unfold, nn.Linear, ReLU, eval BatchNorm1d, torch.std / torch.var
+ * pooling, lin11) with respect to the 22 weights and biases: grad (nplda_xvec_grad_floats() floats) = dL/dparams given
+ * dxvec (n_utts, lddx) = dL/dx-vectors, from the `saved` buffer of the nplda_xvec_extract_train_f32 call with the same
+ * offsets, n_utts, total_frames, pooling and packed image; packed_t from the same weights.  grad is overwritten, not
+ * accumulated.  Deterministic: fixed split-K partition and summation order, no atomics. */
+int nplda_xvec_backward_f32(const void* saved, size_t saved_bytes, const int64_t* offsets, int64_t n_utts,
+                            int64_t total_frames, int pooling, const float* dxvec, int64_t lddx, const void* packed,
+                            const void* packed_t, float* grad, void* ws, size_t ws_bytes, nplda_stream_t stream);
+
 /* ---- measurement utility ------------------------------------------------------------------------------------- */
 
 /* Shader-clock probe for bench.py (no reference counterpart): one wave that stays resident for window_us microseconds

@@ -183,6 +183,15 @@ SIGNATURES = {
     "nplda_xvec_workspace_bytes": (_c_sz, [_c_i64, _c_i64]),
     "nplda_xvec_extract_f32": (_c_int, [_c_f32p, _c_int, _c_i64, _c_vp, _c_i64, _c_i64, _c_int, _c_vp, _c_f32p, _c_i64, _c_vp,
                                         _c_sz, _c_vp]),
+    "nplda_xvec_train_saved_bytes": (_c_sz, [_c_i64, _c_i64]),
+    "nplda_xvec_extract_train_f32": (_c_int, [_c_f32p, _c_int, _c_i64, _c_vp, _c_i64, _c_i64, _c_int, _c_vp, _c_f32p,
+                                              _c_i64, _c_vp, _c_sz, _c_vp]),
+    "nplda_xvec_packed_t_bytes": (_c_sz, []),
+    "nplda_xvec_pack_t_f32": (_c_int, [ctypes.POINTER(ctypes.c_void_p), _c_vp, _c_sz, _c_vp]),
+    "nplda_xvec_grad_floats": (_c_sz, []),
+    "nplda_xvec_backward_workspace_bytes": (_c_sz, [_c_i64, _c_i64]),
+    "nplda_xvec_backward_f32": (_c_int, [_c_vp, _c_sz, _c_vp, _c_i64, _c_i64, _c_int, _c_f32p, _c_i64, _c_vp, _c_vp,
+                                         _c_f32p, _c_vp, _c_sz, _c_vp]),
     "gb_score_pairs_ex_f32": (_c_int, [_c_f32p, _c_f32p, _c_i64, _c_i64, _c_vp, _c_int, _c_int, _c_f32p, _c_f32p,
                                        _c_f32p, _c_vp]),
 }

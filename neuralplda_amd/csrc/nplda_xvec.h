@@ -47,8 +47,7 @@ struct LayerGeom {
 
 inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 
-inline LayerGeom geom(int l, size_t start) {
-    const Layer s = kShape[l];
+inline LayerGeom geom_of(const Layer s, size_t start) {
     LayerGeom g;
     g.Din = s.Din; g.Dout = s.Dout; g.c = s.c; g.d = s.d;
     g.Dinp = round_up(s.Din, 16);
@@ -65,6 +64,8 @@ inline LayerGeom geom(int l, size_t start) {
     g.end = g.oInv + (size_t)g.XBp * 16;
     return g;
 }
+
+inline LayerGeom geom(int l, size_t start) { return geom_of(kShape[l], start); }
 
 inline size_t packed_floats() {
     size_t o = 0;

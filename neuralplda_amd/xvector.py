@@ -8,10 +8,19 @@ hand-written HIP (csrc/nplda_xvec.hip through include/nplda_hip.h):
     extract_ragged(frames, lens)   (sum T_u, 30) frames of utterances of different lengths -> (U, 512)
     Etdnn_Xvec_NeuralPlda.forward  extract both sides, then the existing HIP NPLDA head       (utils/models.py:251-268)
 
-Batch norm runs with its running statistics only (the reference's `train1()` puts the tdnn batch norms in eval mode);
-there is no backward through the extractor: with grad mode on, a parameter of the extractor that requires grad is an
-error, and a frozen extractor (`xvector_extractor.requires_grad_(False)`) trains the head through the head's own HIP
-backward.  The classifier path (`forward`, `prestatspool`, `postpooling`) is not provided.
+Batch norm runs with its running statistics only (the reference's `train1()` puts the tdnn batch norms in eval mode).
+By default there is no backward through the extractor: with grad mode on, a parameter of the extractor that requires
+grad is an error, and a frozen extractor (`xvector_extractor.requires_grad_(False)`) trains the head through the head's
+own HIP backward.
+
+`XVectorNet_ETDNN_12Layer.enable_backward()` (or `Etdnn_Xvec_NeuralPlda.train1(finetune_extractor=True)`) turns on the
+end-to-end path: with grad mode on and an extractor parameter that requires grad, `extract` / `extract_ragged` run a
+training forward (csrc/nplda_xvec_bwd.hip: the same GEMMs, so the same x-vectors bit for bit) that keeps every layer's
+activations and ReLU masks, about 30 KB per frame (`nplda_xvec_train_saved_bytes`: 30.7 KB per frame plus 12 KB per
+utterance) held until backward, and the backward returns the gradients of the 22 tdnn1..tdnn10 / lin11 weights and biases
+through HIP kernels (bn11, bn12, lin12 and finlin keep grad None, as in the reference).  The training path does not
+chunk a batch: one call per side.  There is no dL/dMFCC (an input that requires grad is an error).  The classifier path
+(`forward`, `prestatspool`, `postpooling`) is not provided.
 """
 import ctypes
 import pickle
@@ -98,6 +107,8 @@ class TDNN(nn.Module):
 class XVectorNet_ETDNN_12Layer(nn.Module):
     """utils/models.py:98-214: the 12-layer E-TDNN x-vector network.  `extract` / `extract_ragged` run on HIP."""
 
+    backward_enabled = False  # class attribute: pickles written before the switch existed load with it off
+
     def __init__(self, noclasses=13539, pooling_function=torch.std):
         super(XVectorNet_ETDNN_12Layer, self).__init__()
         for i, (din, dout, c, d) in enumerate(LAYERS, 1):
@@ -131,6 +142,11 @@ class XVectorNet_ETDNN_12Layer(nn.Module):
     def train(self, mode=True):
         self.invalidate_packed()
         return super(XVectorNet_ETDNN_12Layer, self).train(mode)
+
+    def enable_backward(self, flag=True):
+        """Opt in to backpropagation through `extract` / `extract_ragged` (a plain attribute, not state-dict content)."""
+        self.backward_enabled = bool(flag)
+        return self
 
     def forward(self, x):
         raise NotImplementedError("the classifier path (utils/models.py:158-168) is not provided: use extract()")
@@ -180,6 +196,43 @@ class XVectorNet_ETDNN_12Layer(nn.Module):
         cache.update(key=key, srcs=list(srcs), buf=buf)
         return buf
 
+    def _packed_t(self, dev):
+        """The transposed weight image of the data gradient, cached next to `_packed(dev)` under the same key."""
+        self._packed(dev)
+        cache = self.__dict__["_xvec_cache"]
+        if cache.get("buf_t") is None:
+            lib = _lib.load()
+            with _lib.on_device(dev):
+                W = [t.detach().to(dev, torch.float32).contiguous() for t in self._sources()[0]]
+                n = lib.nplda_xvec_packed_t_bytes()
+                buf = torch.empty(n, dtype=torch.uint8, device=dev)
+                ptrs = (ctypes.c_void_p * len(W))(*[t.data_ptr() for t in W])
+                _lib.check(lib.nplda_xvec_pack_t_f32(ptrs, buf.data_ptr(), n, _lib.current_stream(dev)),
+                           "nplda_xvec_pack_t_f32")
+            cache["buf_t"] = buf
+        return cache["buf_t"]
+
+    def _grad_params(self):
+        """tdnn1.W, tdnn1.b, ..., tdnn10.b, lin11.W, lin11.b: the order of nplda_xvec_backward_f32's flat gradient."""
+        out = []
+        for m in [t.kernel for t in self.tdnns()] + [self.lin11]:
+            out += [m.weight, m.bias]
+        return out
+
+    def _wants_backward(self, x):
+        """True when extraction must record for autograd (the switch is on, grad mode is on and an extractor parameter
+        requires grad); raises for what the training path does not provide."""
+        if not (self.backward_enabled and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
+            return False
+        for i, t in enumerate(self.tdnns(), 1):
+            bn = t.bn
+            if bn.training or bn.running_mean is None or bn.running_var is None:
+                raise RuntimeError(f"tdnn{i}.bn is in training mode (batch statistics): the HIP extractor implements "
+                                   "running-statistics batch norm only; call .eval() (or Etdnn_Xvec_NeuralPlda.train1())")
+        if x.requires_grad:
+            raise RuntimeError("no backward through the x-vector extractor: its input must not require grad")
+        return True
+
     # -- extraction ------------------------------------------------------------------------------
     def _run(self, x, layout, lengths, dev, workspace_bytes):
         """x on `dev`, float32 contiguous: (sum T, 30) for LAYOUT_ROWS, (U, 30, T) for LAYOUT_BCT."""
@@ -210,13 +263,18 @@ class XVectorNet_ETDNN_12Layer(nn.Module):
         on the HIP device (CPU input is staged through it and the result returned on the input's device)."""
         if x.dim() != 3 or x.shape[1] != FEAT:
             raise ValueError(f"extract expects (B, {FEAT}, T) features, got {tuple(x.shape)}")
-        self._check_mode(x)
+        grad = self._wants_backward(x)
+        if not grad:
+            self._check_mode(x)
         B, _, T = x.shape
         if B > 0 and T <= CONTEXT:
             raise ValueError(f"T = {T} frames is shorter than the extractor's context ({CONTEXT + 1} frames at least)")
         dev = _compute_device(x, self.lin11.weight)
         X = x.detach().to(dev, torch.float32).contiguous()
-        out = self._run(X, LAYOUT_BCT, [T] * B, dev, workspace_bytes)
+        if grad:
+            out = _ExtractFn.apply(self, X, LAYOUT_BCT, [T] * B, dev, *self._grad_params())
+        else:
+            out = self._run(X, LAYOUT_BCT, [T] * B, dev, workspace_bytes)
         return out if out.device == x.device else out.to(x.device)
 
     def extract_ragged(self, frames, lengths, workspace_bytes=None):
@@ -231,10 +289,15 @@ class XVectorNet_ETDNN_12Layer(nn.Module):
         if short:
             raise ValueError(f"an utterance of {short[0]} frames is shorter than the extractor's context "
                              f"({CONTEXT + 1} frames at least; the reference's unfold raises)")
-        self._check_mode(frames)
+        grad = self._wants_backward(frames)
+        if not grad:
+            self._check_mode(frames)
         dev = _compute_device(frames, self.lin11.weight)
         X = frames.detach().to(dev, torch.float32).contiguous()
-        out = self._run(X, LAYOUT_ROWS, lengths, dev, workspace_bytes)
+        if grad:
+            out = _ExtractFn.apply(self, X, LAYOUT_ROWS, lengths, dev, *self._grad_params())
+        else:
+            out = self._run(X, LAYOUT_ROWS, lengths, dev, workspace_bytes)
         return out if out.device == frames.device else out.to(frames.device)
 
     # -- Kaldi -----------------------------------------------------------------------------------
@@ -265,6 +328,50 @@ class XVectorNet_ETDNN_12Layer(nn.Module):
         self.invalidate_packed()
 
 
+class _ExtractFn(torch.autograd.Function):
+    """extract / extract_ragged with a backward to the 22 tdnn1..tdnn10 / lin11 parameters (inputs after the first
+    five, in `_grad_params` order).  The saved buffer (~30 KB per frame) lives from forward to backward."""
+
+    @staticmethod
+    def forward(ctx, ext, X, layout, lengths, dev, *params):
+        U, R = len(lengths), int(sum(lengths))
+        kind = _pool_kind(ext.pooling_function)
+        packed, packed_t = ext._packed(dev), ext._packed_t(dev)
+        lib = _lib.load()
+        starts = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+        out = torch.empty((U, XVEC_DIM), dtype=torch.float32, device=dev)
+        with _lib.on_device(dev):
+            offs = torch.from_numpy(starts).to(dev)
+            n = lib.nplda_xvec_train_saved_bytes(R, U)
+            saved = torch.empty(n, dtype=torch.uint8, device=dev)
+            _lib.check(lib.nplda_xvec_extract_train_f32(X.data_ptr(), layout, FEAT, offs.data_ptr(), U, R, kind,
+                                                        packed.data_ptr(), out.data_ptr(), XVEC_DIM, saved.data_ptr(), n,
+                                                        _lib.current_stream(dev)), "nplda_xvec_extract_train_f32")
+        ctx.state = (saved, offs, packed, packed_t, R, U, kind, dev, [tuple(p.shape) for p in params])
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        saved, offs, packed, packed_t, R, U, kind, dev, shapes = ctx.state
+        lib = _lib.load()
+        with _lib.on_device(dev):
+            d = dout.detach().to(dev, torch.float32).contiguous()
+            grad = torch.empty(lib.nplda_xvec_grad_floats(), dtype=torch.float32, device=dev)
+            n = lib.nplda_xvec_backward_workspace_bytes(R, U)
+            ws = torch.empty(n, dtype=torch.uint8, device=dev)
+            _lib.check(lib.nplda_xvec_backward_f32(saved.data_ptr(), saved.numel(), offs.data_ptr(), U, R, kind,
+                                                   d.data_ptr(), XVEC_DIM, packed.data_ptr(), packed_t.data_ptr(),
+                                                   grad.data_ptr(), ws.data_ptr(), n, _lib.current_stream(dev)),
+                       "nplda_xvec_backward_f32")
+        grads, o = [], 0
+        for sh in shapes:
+            k = int(np.prod(sh))
+            grads.append(grad[o:o + k].view(sh))
+            o += k
+        ctx.state = None
+        return (None,) * 5 + tuple(grads)
+
+
 class Etdnn_Xvec_NeuralPlda(NeuralPlda):
     """utils/models.py:216-345: the NPLDA head on an E-TDNN extractor.  `nc` is an E2EConf (or any object with its
     xvector_dim, layer1_LDA_dim, layer2_PLDA_spkfactor_dim, pooling_function, beta, alpha, device, loss).  The head's
@@ -279,11 +386,15 @@ class Etdnn_Xvec_NeuralPlda(NeuralPlda):
         self._modules = type(mods)([("xvector_extractor", mods["xvector_extractor"])] +
                                    [(k, v) for k, v in mods.items() if k != "xvector_extractor"])
 
-    def train1(self):
-        """utils/models.py:231-242: training mode with the tdnn batch norms on their running statistics."""
+    def train1(self, finetune_extractor=None):
+        """utils/models.py:231-242: training mode with the tdnn batch norms on their running statistics.
+        finetune_extractor: None leaves XVectorNet_ETDNN_12Layer.enable_backward's switch as it is; True / False sets it
+        (True: a trainable extractor is trained end to end through the HIP backward)."""
         self.train()
         for t in self.xvector_extractor.tdnns():
             t.bn.training = False
+        if finetune_extractor is not None:
+            self.xvector_extractor.enable_backward(finetune_extractor)
         return self
 
     def extract_plda_embeddings(self, x):
