@@ -675,6 +675,51 @@ int nplda_xvec_backward_f32(const void* saved, size_t saved_bytes, const int64_t
                             int64_t total_frames, int pooling, const float* dxvec, int64_t lddx, const void* packed,
                             const void* packed_t, float* grad, void* ws, size_t ws_bytes, nplda_stream_t stream);
 
+/* ---- feature front end of the extractor (Kaldi feature archives -> its input rows) ------------------------------ */
+
+/* csrc/nplda_feat.hip: what the x-vector recipe runs in front of nnet3-xvector-compute, `apply-cmvn-sliding
+ * --norm-vars=false --center=true --cmn-window=300 | select-voiced-frames` over feats.scp and vad.scp (or
+ * compute-vad-energy with the options of vad.conf), on matrix bodies copied from the archive as they are
+ * (neuralplda_amd/kaldi_format.py load_feature_scp).  design/k13_feature_frontend.md. */
+#define NPLDA_FEAT_DIM 30  /* columns of every matrix (the extractor's input dimension) */
+#define NPLDA_FEAT_FM  0   /* float32 rows                                                         */
+#define NPLDA_FEAT_DM  1   /* float64 rows                                                         */
+#define NPLDA_FEAT_CM  2   /* Kaldi CompressedMatrix, one byte per value, column-major, per-column headers */
+#define NPLDA_FEAT_CM2 3   /* uint16 per value, row-major                                          */
+#define NPLDA_FEAT_CM3 4   /* uint8 per value, row-major                                           */
+/* One matrix of the payload.  Offsets are bytes from the start of the payload; data_off is a multiple of the element size
+ * (4 FM, 8 DM, 2 CM2), hdr_off (CM only: cols x four uint16 percentiles) is even.  min_value / range: CM, CM2, CM3. */
+typedef struct nplda_feat_desc {
+    int32_t format, rows, cols;
+    float min_value, range;
+    int32_t reserved;
+    int64_t hdr_off, data_off;
+} nplda_feat_desc;
+
+/* frames (total_frames, 30) float32 = the n_utts matrices of `desc` (device array of nplda_feat_desc) decoded from `payload`
+ * (device bytes, 8-byte aligned), one launch.  offsets: int64 device array of n_utts + 1 frame offsets, offsets[u + 1] -
+ * offsets[u] == desc[u].rows, offsets[n_utts] == total_frames.  An entry whose body does not lie inside payload_bytes, is
+ * misaligned, has cols != 30 or an unknown format decodes to NaN rows (nothing outside the payload is read). */
+int nplda_feat_decode_f32(const void* payload, size_t payload_bytes, const void* desc, const int64_t* offsets, int64_t n_utts,
+                          int64_t total_frames, float* frames, nplda_stream_t stream);
+/* compute-vad-energy on column 0: thr_u = energy_threshold + energy_mean_scale * mean_t frames[u][t][0] (fp64, fixed order);
+ * mask[t] = 1 iff, over t2 in [t - frames_context, t + frames_context] clipped to the utterance, the number of frames
+ * with c0 > thr_u is >= (number of t2) * proportion_threshold.  mask: (total_frames) bytes. */
+int nplda_feat_vad_energy_f32(const float* frames, const int64_t* offsets, int64_t n_utts, int64_t total_frames,
+                              double energy_threshold, double energy_mean_scale, double proportion_threshold,
+                              int frames_context, uint8_t* mask, nplda_stream_t stream);
+/* Workspace of one nplda_feat_cmn_select_f32 call (fp64 prefix sums: 240 bytes per frame and per utterance). */
+size_t nplda_feat_workspace_bytes(int64_t total_frames, int64_t n_utts);
+/* Sliding-window mean subtraction, then selection of the voiced frames, in that order.  Frame t of a T-frame utterance
+ * loses the mean of frames [s, e): s = t - cmn_window / 2, e = s + cmn_window, shifted into [0, T) and cut to it (fp64
+ * prefix sums in a fixed order); cmn_window == 0: no subtraction.  mask: (total_frames) bytes, non-zero = keep; NULL keeps
+ * every frame.  counts[u] (int32, n_utts) = kept frames of utterance u.  Utterances with counts[u] >= min_frames are
+ * written to `out` one after the other, their kept frames in order ((sum of those counts, 30) float32, at most
+ * total_frames rows); the others are left out.  Same bits on every call; an utterance's rows do not depend on the batch. */
+int nplda_feat_cmn_select_f32(const float* frames, const int64_t* offsets, int64_t n_utts, int64_t total_frames,
+                              const uint8_t* mask, int cmn_window, int min_frames, float* out, int32_t* counts, void* ws,
+                              size_t ws_bytes, nplda_stream_t stream);
+
 /* ---- measurement utility ------------------------------------------------------------------------------------- */
 
 /* Shader-clock probe for bench.py (no reference counterpart): one wave that stays resident for window_us microseconds

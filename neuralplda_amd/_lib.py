@@ -192,6 +192,12 @@ SIGNATURES = {
     "nplda_xvec_backward_workspace_bytes": (_c_sz, [_c_i64, _c_i64]),
     "nplda_xvec_backward_f32": (_c_int, [_c_vp, _c_sz, _c_vp, _c_i64, _c_i64, _c_int, _c_f32p, _c_i64, _c_vp, _c_vp,
                                          _c_f32p, _c_vp, _c_sz, _c_vp]),
+    "nplda_feat_decode_f32": (_c_int, [_c_vp, _c_sz, _c_vp, _c_vp, _c_i64, _c_i64, _c_f32p, _c_vp]),
+    "nplda_feat_vad_energy_f32": (_c_int, [_c_f32p, _c_vp, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                           _c_int, _c_vp, _c_vp]),
+    "nplda_feat_workspace_bytes": (_c_sz, [_c_i64, _c_i64]),
+    "nplda_feat_cmn_select_f32": (_c_int, [_c_f32p, _c_vp, _c_i64, _c_i64, _c_vp, _c_int, _c_int, _c_f32p, _c_vp, _c_vp,
+                                           _c_sz, _c_vp]),
     "gb_score_pairs_ex_f32": (_c_int, [_c_f32p, _c_f32p, _c_i64, _c_i64, _c_vp, _c_int, _c_int, _c_f32p, _c_f32p,
                                        _c_f32p, _c_vp]),
 }

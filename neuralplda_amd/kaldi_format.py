@@ -5,6 +5,10 @@ utils/models.py:442-448, utils/Kaldi2NumpyUtils/kaldiPlda2numpydict.py:17) and p
 output.  This module reads the same files directly — binary (`\\0B` + `FM `/`DM `/`FV `/`DV `
 tokens, `\\x04`+int32 sizes, little-endian payload) or Kaldi text (`[ ... ]`) — so no Kaldi
 installation is needed.  It is host-side file I/O only.
+
+Feature matrices (`feats.scp` of a Kaldi data directory) are read too, including the compressed forms `CM` / `CM2` / `CM3`
+that `make_mfcc.sh` writes by default: `read_matrix` decodes one on the host, `load_feature_scp` collects the raw bodies of
+many into one buffer for the device decoder (neuralplda_amd/features.py, design/k13_feature_frontend.md).
 """
 import io
 import os
@@ -14,7 +18,8 @@ import numpy as np
 
 __all__ = ["read_vector", "read_matrix", "read_plda", "plda_psi_to_pq", "read_vector_ark", "read_vector_scp",
            "read_scp", "load_vector_ark", "load_vector_scp", "write_vector_ark", "fold_init",
-           "write_matrix_binary", "write_vector_binary", "write_plda_binary"]
+           "write_matrix_binary", "write_vector_binary", "write_plda_binary", "read_feature_ark", "read_feature_scp",
+           "load_feature_scp", "FeatureArchive", "FEAT_DESC", "FEAT_FORMATS", "KaldiFormatError"]
 
 
 class KaldiFormatError(ValueError):
@@ -76,11 +81,50 @@ def _read_binary_vector_body(fh, tok):
     return np.frombuffer(buf, dtype=dt).astype(np.float64)
 
 
+# Kaldi compressed-matrix.h, global header after the token: float min_value, float range, int32 num_rows, int32 num_cols
+# (no \\x04 size markers).  CM: num_cols x four uint16 percentiles, then num_rows * num_cols bytes COLUMN-major; CM2: uint16
+# row-major; CM3: uint8 row-major.
+_CM_HEADER = struct.Struct("<ffii")
+
+
+def _u16_to_float(min_value, rng, v):
+    return min_value + rng * (1.0 / 65535.0) * v
+
+
+def _decode_compressed(tok, min_value, rng, rows, cols, buf):
+    """Body bytes of a CM / CM2 / CM3 matrix -> float64 (rows, cols)."""
+    min_value, rng = float(min_value), float(rng)
+    if tok == "CM2":
+        return _u16_to_float(min_value, rng, np.frombuffer(buf, dtype="<u2").astype(np.float64)).reshape(rows, cols)
+    if tok == "CM3":
+        return (min_value + rng * (np.frombuffer(buf, dtype=np.uint8).astype(np.float64) / 255.0)).reshape(rows, cols)
+    p = _u16_to_float(min_value, rng, np.frombuffer(buf, dtype="<u2", count=4 * cols).astype(np.float64)).reshape(cols, 4)
+    b = np.frombuffer(buf, dtype=np.uint8, offset=8 * cols).astype(np.float64).reshape(cols, rows)
+    p0, p25, p75, p100 = (p[:, i:i + 1] for i in range(4))
+    out = np.where(b <= 64, p0 + (p25 - p0) * b / 64.0,
+                   np.where(b <= 192, p25 + (p75 - p25) * (b - 64.0) / 128.0, p75 + (p100 - p75) * (b - 192.0) / 63.0))
+    return np.ascontiguousarray(out.T)
+
+
+def _compressed_body_bytes(tok, rows, cols):
+    return {"CM": 8 * cols + rows * cols, "CM2": 2 * rows * cols, "CM3": rows * cols}[tok]
+
+
 def _read_binary_matrix_body(fh, tok):
-    if tok == "CM" or tok.startswith("CM"):
-        raise KaldiFormatError("compressed Kaldi matrices (CM) are not supported")
+    if tok in ("CM", "CM2", "CM3"):
+        hdr = fh.read(_CM_HEADER.size)
+        if len(hdr) != _CM_HEADER.size:
+            raise KaldiFormatError("truncated compressed-matrix header")
+        min_value, rng, r, c = _CM_HEADER.unpack(hdr)
+        if r < 0 or c < 0:
+            raise KaldiFormatError(f"compressed matrix of {r} x {c}")
+        n = _compressed_body_bytes(tok, r, c)
+        buf = fh.read(n)
+        if len(buf) != n:
+            raise KaldiFormatError("truncated matrix payload")
+        return _decode_compressed(tok, min_value, rng, r, c, buf)
     if tok not in ("FM", "DM"):
-        raise KaldiFormatError(f"expected FM/DM matrix token, got {tok!r}")
+        raise KaldiFormatError(f"expected FM/DM/CM/CM2/CM3 matrix token, got {tok!r}")
     dt = np.dtype("<f4") if tok == "FM" else np.dtype("<f8")
     r = _read_int32(fh)
     c = _read_int32(fh)
@@ -138,7 +182,7 @@ def read_vector(f):
 
 
 def read_matrix(f):
-    """Kaldi Matrix<float|double>, binary or text (e.g. Kaldi_Models/transform.mat) -> float64 (r, c)."""
+    """Kaldi Matrix<float|double> or CompressedMatrix, binary or text (e.g. Kaldi_Models/transform.mat) -> float64 (r, c)."""
     fh, close = _open(f)
     try:
         if _is_binary(fh):
@@ -385,6 +429,140 @@ def write_vector_ark(ark_path, keys, mat, scp_path=None):
         with open(scp_path, "w") as fh:
             fh.write("".join(f"{k} {ark_path}:{o}\n" for k, o in zip(keys, offsets)))
     return offsets
+
+
+# ---- feature-matrix archives (feats.scp) ---------------------------------------------------------------------------
+#
+# The per-utterance loop of a feature reader (kaldi_io.read_mat per scp line, then NumPy per matrix) is what this avoids:
+# the bodies are copied as they lie on disk into ONE buffer, and a descriptor per matrix tells the device decoder
+# (csrc/nplda_feat.hip) where each is.  A CM matrix costs one byte per value on the way to the device, not four.
+
+FEAT_FORMATS = {"FM": 0, "DM": 1, "CM": 2, "CM2": 3, "CM3": 4}  # include/nplda_hip.h NPLDA_FEAT_*
+# nplda_feat_desc of include/nplda_hip.h (40 bytes); offsets in bytes from the start of the payload
+FEAT_DESC = np.dtype([("format", "<i4"), ("rows", "<i4"), ("cols", "<i4"), ("min_value", "<f4"), ("range", "<f4"),
+                      ("reserved", "<i4"), ("hdr_off", "<i8"), ("data_off", "<i8")])
+_FEAT_ALIGN = 16  # every body starts on a 16-byte boundary of the payload (the decoder reads floats and doubles in place)
+
+
+class FeatureArchive(tuple):
+    """(keys, desc, payload) of load_feature_scp: keys in scp order, desc a FEAT_DESC array (one entry per key), payload
+    ONE contiguous uint8 array holding the raw matrix bodies."""
+    __slots__ = ()
+
+    def __new__(cls, keys, desc, payload):
+        return tuple.__new__(cls, (keys, desc, payload))
+
+    keys = property(lambda self: self[0])
+    desc = property(lambda self: self[1])
+    payload = property(lambda self: self[2])
+
+    def body(self, i):
+        """The bytes of matrix i's data (for CM: without the per-column headers) as a view of the payload."""
+        d = self.desc[i]
+        esz = {0: 4, 1: 8, 2: 1, 3: 2, 4: 1}[int(d["format"])]
+        return self.payload[int(d["data_off"]):int(d["data_off"]) + esz * int(d["rows"]) * int(d["cols"])]
+
+
+def _matrix_header_at(buf, off, key):
+    """(token, min_value, range, rows, cols, position of the body) of the binary matrix object at byte `off` of `buf`."""
+    total = len(buf)
+    head = bytes(buf[off:off + 32])
+    if head[:2] != b"\0B":
+        raise KaldiFormatError(f"{key}: not a binary Kaldi object at offset {off} (text-mode feature archives are not read)")
+    sp = head.find(b" ", 2)
+    tok = head[2:sp].decode("ascii", "replace") if sp > 0 else head[2:6].decode("ascii", "replace")
+    pos = off + sp + 1
+    if tok in ("FM", "DM"):
+        if pos + 10 > total or buf[pos] != 4 or buf[pos + 5] != 4:
+            raise KaldiFormatError(f"{key}: truncated or malformed {tok} header")
+        r, c = struct.unpack("<i", bytes(buf[pos + 1:pos + 5]))[0], struct.unpack("<i", bytes(buf[pos + 6:pos + 10]))[0]
+        return tok, 0.0, 0.0, r, c, pos + 10
+    if tok in ("CM", "CM2", "CM3"):
+        if pos + _CM_HEADER.size > total:
+            raise KaldiFormatError(f"{key}: truncated {tok} header")
+        mn, rg, r, c = _CM_HEADER.unpack(bytes(buf[pos:pos + _CM_HEADER.size]))
+        return tok, mn, rg, r, c, pos + _CM_HEADER.size
+    raise KaldiFormatError(f"{key}: unknown matrix token {tok!r} (expected FM, DM, CM, CM2 or CM3)")
+
+
+def _body_bytes(tok, r, c):
+    if tok in ("FM", "DM"):
+        return r * c * (4 if tok == "FM" else 8)
+    return _compressed_body_bytes(tok, r, c)
+
+
+def read_feature_ark(f):
+    """Iterate (key, float32 (T, D) matrix) over a binary Kaldi matrix archive whose entries are FM, DM, CM, CM2 or CM3,
+    freely mixed (decoded on the host: a convenience; the bulk path is load_feature_scp + features.prepare_features)."""
+    fh, close = _open(f)
+    try:
+        while True:
+            key = _read_token(fh)
+            if key == "":
+                return
+            if not _is_binary(fh):
+                raise KaldiFormatError(f"{key}: text-mode feature archives are not read")
+            try:
+                mat = _read_binary_matrix_body(fh, _read_token(fh))
+            except KaldiFormatError as e:
+                raise KaldiFormatError(f"{key}: {e}") from None
+            yield key, mat.astype(np.float32)
+    finally:
+        if close:
+            fh.close()
+
+
+def read_feature_scp(path):
+    """Iterate (key, float32 (T, D) matrix) over a Kaldi scp of feature matrices ('ark:offset' or one-matrix files)."""
+    maps = {}
+    for key, rx in read_scp(path):
+        f, off = _split_rx(rx)
+        if f not in maps:
+            maps[f] = np.memmap(_scp_file(f, path), dtype=np.uint8, mode="r")
+        buf = maps[f]
+        tok, mn, rg, r, c, pos = _matrix_header_at(buf, off or 0, key)
+        n = _body_bytes(tok, r, c)
+        if r < 0 or c < 0 or pos + n > len(buf):
+            raise KaldiFormatError(f"{key}: truncated matrix payload ({tok} {r} x {c})")
+        body = bytes(buf[pos:pos + n])
+        if tok in ("FM", "DM"):
+            mat = np.frombuffer(body, dtype="<f4" if tok == "FM" else "<f8").reshape(r, c)
+        else:
+            mat = _decode_compressed(tok, mn, rg, r, c, body)
+        yield key, mat.astype(np.float32)
+
+
+def load_feature_scp(path, entries=None, cols=None):
+    """Kaldi scp of feature matrices -> FeatureArchive(keys, desc, payload) WITHOUT decoding: each archive is memory-mapped
+    once and every entry's body (for CM: per-column headers, then data) is copied as it is into one uint8 buffer, each on a
+    16-byte boundary.  `entries`: a slice of read_scp(path) to load instead of the whole file (bounded pieces of a large
+    scp).  `cols`: if given, a matrix with another number of columns is an error naming the key."""
+    if entries is None:
+        entries = read_scp(path)
+    n = len(entries)
+    desc = np.zeros(n, dtype=FEAT_DESC)
+    maps, src = {}, []
+    total = 0
+    for i, (key, rx) in enumerate(entries):
+        f, off = _split_rx(rx)
+        if f not in maps:
+            maps[f] = np.memmap(_scp_file(f, path), dtype=np.uint8, mode="r")
+        buf = maps[f]
+        tok, mn, rg, r, c, pos = _matrix_header_at(buf, off or 0, key)
+        nb = _body_bytes(tok, r, c)
+        if r < 0 or c < 0 or pos + nb > len(buf):
+            raise KaldiFormatError(f"{key}: truncated matrix payload ({tok} {r} x {c} needs {nb} bytes at {pos}, the archive "
+                                   f"has {len(buf)})")
+        if cols is not None and c != cols:
+            raise KaldiFormatError(f"{key}: matrix of {c} columns, expected {cols}")
+        hdr = 8 * c if tok == "CM" else 0
+        desc[i] = (FEAT_FORMATS[tok], r, c, mn, rg, 0, total, total + hdr)
+        src.append((buf, pos, nb, total))
+        total += (nb + _FEAT_ALIGN - 1) // _FEAT_ALIGN * _FEAT_ALIGN
+    payload = np.zeros(total, dtype=np.uint8)
+    for buf, pos, nb, at in src:
+        payload[at:at + nb] = buf[pos:pos + nb]
+    return FeatureArchive([k for k, _ in entries], desc, payload)
 
 
 # ---- Kaldi initialisation of the model classes --------------------------------------------------------------------

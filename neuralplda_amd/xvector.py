@@ -6,6 +6,7 @@ hand-written HIP (csrc/nplda_xvec.hip through include/nplda_hip.h):
 
     extract(x)                     (B, 30, T) features -> (B, 512) x-vectors                 (utils/models.py:170-186)
     extract_ragged(frames, lens)   (sum T_u, 30) frames of utterances of different lengths -> (U, 512)
+    extract_from_scp(feats_scp)    a Kaldi feature scp (+ VAD) -> keys, (U, 512): features.py's front end, then extract_ragged
     Etdnn_Xvec_NeuralPlda.forward  extract both sides, then the existing HIP NPLDA head       (utils/models.py:251-268)
 
 Batch norm runs with its running statistics only (the reference's `train1()` puts the tdnn batch norms in eval mode).
@@ -23,13 +24,14 @@ chunk a batch: one call per side.  There is no dL/dMFCC (an input that requires 
 (`forward`, `prestatspool`, `postpooling`) is not provided.
 """
 import ctypes
+import os
 import pickle
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, kaldi_format
+from . import _lib, features, kaldi_format
 from .models import NeuralPlda, _compute_device
 
 __all__ = ["TDNN", "XVectorNet_ETDNN_12Layer", "Etdnn_Xvec_NeuralPlda", "LAYERS", "CONTEXT", "flops_per_frame"]
@@ -299,6 +301,48 @@ class XVectorNet_ETDNN_12Layer(nn.Module):
         else:
             out = self._run(X, LAYOUT_ROWS, lengths, dev, workspace_bytes)
         return out if out.device == frames.device else out.to(frames.device)
+
+    def extract_from_scp(self, feats_scp, vad=features.VadOptions(), cmn_window=300, min_frames=25, utts_per_call=2048,
+                         device=None):
+        """The recipe's `apply-cmvn-sliding | select-voiced-frames | nnet3-xvector-compute` over a Kaldi feats.scp (FM, DM,
+        CM, CM2, CM3 entries): -> (keys, (len(keys), 512) x-vectors on the device, dropped).  vad: features.VadOptions
+        (energy VAD on the device), a {key: 0/1 vector} dict, the path of a vad.scp, or None to keep every frame.
+        Utterances with fewer than min_frames (>= 24, the extractor's context plus two) voiced frames are not extracted:
+        they come back in `dropped` as (key, voiced frames).  The scp is worked through utts_per_call lines at a time, so
+        that the host payload, its device copy and the workspaces stay bounded; the pieces do not change the result (bit
+        for bit).  Inference only (runs under torch.no_grad())."""
+        if int(min_frames) < CONTEXT + 2:
+            raise ValueError(f"min_frames = {min_frames}: the extractor needs {CONTEXT + 2} frames at least")
+        if int(utts_per_call) < 1:
+            raise ValueError("utts_per_call must be positive")
+        dev = _compute_device(self.lin11.weight) if device is None else torch.device(device)
+        vad_index, maps = None, {}
+        if isinstance(vad, (str, os.PathLike)):
+            vad_index = dict(kaldi_format.read_scp(vad))
+        entries = kaldi_format.read_scp(feats_scp)
+        keys, dropped, parts = [], [], []
+        for lo in range(0, len(entries), int(utts_per_call)):
+            piece = entries[lo:lo + int(utts_per_call)]
+            feats = kaldi_format.load_feature_scp(feats_scp, entries=piece, cols=FEAT)
+            v = vad
+            if vad_index is not None:
+                v = {}
+                for k, _ in piece:
+                    if k not in vad_index:
+                        raise KeyError(f"{k}: not in {vad}")
+                    f, off = kaldi_format._split_rx(vad_index[k])
+                    if f not in maps:
+                        maps[f] = np.memmap(kaldi_format._scp_file(f, vad), dtype=np.uint8, mode="r")
+                    v[k] = kaldi_format._vec_at(maps[f], off or 0)
+            prep = features.prepare_features(feats, vad=v, cmn_window=cmn_window, min_frames=min_frames, device=dev)
+            keys += prep.keys
+            dropped += prep.dropped
+            if prep.keys:
+                with torch.no_grad():
+                    parts.append(self.extract_ragged(prep.frames, prep.lengths))
+        if not parts:
+            return keys, torch.empty((0, XVEC_DIM), dtype=torch.float32, device=dev), dropped
+        return keys, (parts[0] if len(parts) == 1 else torch.cat(parts)), dropped
 
     # -- Kaldi -----------------------------------------------------------------------------------
     def LoadFromKaldi(self, weightspath):
