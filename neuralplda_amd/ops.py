@@ -4,6 +4,7 @@ Every function takes torch tensors that live on a HIP device, enqueues the kerne
 current stream and returns torch tensors.  No CPU path exists: a CPU tensor is an error here
 (neuralplda_amd.models stages CPU inputs through the device, it never computes on the host).
 """
+import ctypes
 import functools
 
 import torch
@@ -50,6 +51,15 @@ def _rows(t, name, D0):
     return t, ld
 
 
+def _pair_rows(x1, x2, D0, n1="x1", n2="x2"):
+    """_rows on both sides of a pair batch -> (x1, x2, ld) with ONE row stride: contiguous copies where the two differ."""
+    x1, ld1 = _rows(x1, n1, D0)
+    x2, ld2 = _rows(x2, n2, D0)
+    if ld1 != ld2:
+        x1, x2, ld1 = x1.contiguous(), x2.contiguous(), D0
+    return x1, x2, ld1
+
+
 def pack_params(W1, b1, W2, b2, P_sqrt, Q, precision="fp32"):
     """nplda_pack_params_f32 (or nplda_pack_params_bf16x3): nn.Linear-layout parameters -> PackedParams."""
     lib = _lib.load()
@@ -70,10 +80,10 @@ def pack_params(W1, b1, W2, b2, P_sqrt, Q, precision="fp32"):
             f"model {D0}->{D1}->{D2} is outside the compiled kernel set (max dim {lib.nplda_max_dim()})")
     buf = torch.empty(nbytes // 4, dtype=torch.float32, device=W1.device)
     ts = [t.detach().contiguous() for t in (W1, b1, W2, b2, P_sqrt, Q)]
-    fn = lib.nplda_pack_params_bf16x3 if b3 else lib.nplda_pack_params_f32
+    name = "nplda_pack_params_bf16x3" if b3 else "nplda_pack_params_f32"
     with _lib.on_device(W1.device):
-        code = fn(*[_lib.ptr(t) for t in ts], D0, D1, D2, _lib.ptr(buf), nbytes, _lib.current_stream())
-    _lib.check(code, "nplda_pack_params_bf16x3" if b3 else "nplda_pack_params_f32")
+        code = getattr(lib, name)(*[_lib.ptr(t) for t in ts], D0, D1, D2, _lib.ptr(buf), nbytes, _lib.current_stream())
+    _lib.check(code, name)
     return PackedParams(buf, D0, D1, D2, lib.nplda_padded_dim(D1, D2), precision)
 
 
@@ -101,22 +111,18 @@ def score_pairs(x1, x2, packed):
         x1 = x1.float()
     if torch.is_tensor(x2) and x2.is_floating_point() and x2.dtype != torch.float32:
         x2 = x2.float()
-    x1, ld1 = _rows(x1, "x1", packed.D0)
-    x2, ld2 = _rows(x2, "x2", packed.D0)
+    x1, x2, ld = _pair_rows(x1, x2, packed.D0)
     if x1.shape[0] != x2.shape[0]:
         raise ValueError("x1 and x2 must have the same number of rows")
-    if ld1 != ld2:
-        x1, x2 = x1.contiguous(), x2.contiguous()
-        ld1 = ld2 = packed.D0
     B = x1.shape[0]
     s = torch.empty(B, dtype=torch.float32, device=x1.device)
     if B == 0:
         return s
-    fn = lib.nplda_score_pairs_bf16x3 if packed.precision == "bf16x3" else lib.nplda_score_pairs_f32
+    name = "nplda_score_pairs_bf16x3" if packed.precision == "bf16x3" else "nplda_score_pairs_f32"
     with _lib.on_device(x1.device):
-        code = fn(_lib.ptr(x1), _lib.ptr(x2), B, ld1, _lib.ptr(packed.buf), packed.D0, packed.D1, packed.D2,
-                  _lib.ptr(s), _lib.current_stream())
-    _lib.check(code, "nplda_score_pairs_" + ("bf16x3" if packed.precision == "bf16x3" else "f32"))
+        code = getattr(lib, name)(_lib.ptr(x1), _lib.ptr(x2), B, ld, _lib.ptr(packed.buf), packed.D0, packed.D1, packed.D2,
+                                  _lib.ptr(s), _lib.current_stream())
+    _lib.check(code, name)
     return s
 
 
@@ -138,7 +144,7 @@ def score_pairs_rows(table, rows1, rows2, packed):
         code = lib.nplda_score_pairs_rows_f32(_lib.ptr(table), table.shape[0], ldt, _lib.ptr(rows1), _lib.ptr(rows2), B,
                                               _lib.ptr(packed.buf), packed.D0, packed.D1, packed.D2, _lib.ptr(s),
                                               _lib.current_stream())
-    if code == -95:  # NPLDA_EUNSUPPORTED: a shape the balanced-tile kernel does not cover
+    if code == _lib.NPLDA_EUNSUPPORTED:  # a shape the balanced-tile kernel does not cover
         return score_pairs(gather_rows(table, rows1), gather_rows(table, rows2), packed)
     _lib.check(code, "nplda_score_pairs_rows_f32")
     return s
@@ -153,11 +159,11 @@ def embed(x, packed, want_q=True):
     q = torch.empty(N, dtype=torch.float32, device=x.device) if want_q else None
     if N == 0:
         return z, q
-    fn = lib.nplda_embed_bf16x3 if packed.precision == "bf16x3" else lib.nplda_embed_f32
+    name = "nplda_embed_bf16x3" if packed.precision == "bf16x3" else "nplda_embed_f32"
     with _lib.on_device(x.device):
-        code = fn(_lib.ptr(x), N, ld, _lib.ptr(packed.buf), packed.D0, packed.D1, packed.D2, _lib.ptr(z), packed.ldz,
-                  _lib.ptr(q), _lib.current_stream())
-    _lib.check(code, "nplda_embed_" + ("bf16x3" if packed.precision == "bf16x3" else "f32"))
+        code = getattr(lib, name)(_lib.ptr(x), N, ld, _lib.ptr(packed.buf), packed.D0, packed.D1, packed.D2, _lib.ptr(z),
+                                  packed.ldz, _lib.ptr(q), _lib.current_stream())
+    _lib.check(code, name)
     return z, q
 
 
@@ -220,13 +226,9 @@ def forward_train(x1, x2, packed):
     Returns (s, saved) with saved = (x1, x2, ld, y, z, rn) device tensors."""
     lib = _lib.load()
     _need_fp32(packed, "forward_train")
-    x1, ld1 = _rows(x1, "x1", packed.D0)
-    x2, ld2 = _rows(x2, "x2", packed.D0)
+    x1, x2, ld = _pair_rows(x1, x2, packed.D0)
     if x1.shape[0] != x2.shape[0]:
         raise ValueError("x1 and x2 must have the same number of rows")
-    if ld1 != ld2:
-        x1, x2 = x1.contiguous(), x2.contiguous()
-        ld1 = ld2 = packed.D0
     B = x1.shape[0]
     dev = x1.device
     s = torch.empty(B, dtype=torch.float32, device=dev)
@@ -235,11 +237,11 @@ def forward_train(x1, x2, packed):
     rn = torch.empty(2 * B, dtype=torch.float32, device=dev)
     if B > 0:
         with _lib.on_device(dev):
-            code = lib.nplda_forward_train_f32(_lib.ptr(x1), _lib.ptr(x2), B, ld1, _lib.ptr(packed.buf), packed.D0,
+            code = lib.nplda_forward_train_f32(_lib.ptr(x1), _lib.ptr(x2), B, ld, _lib.ptr(packed.buf), packed.D0,
                                                packed.D1, packed.D2, _lib.ptr(s), _lib.ptr(y), _lib.ptr(z),
                                                _lib.ptr(rn), packed.ldz, _lib.current_stream())
         _lib.check(code, "nplda_forward_train_f32")
-    return s, (x1, x2, ld1, y, z, rn)
+    return s, (x1, x2, ld, y, z, rn)
 
 
 @functools.lru_cache(maxsize=64)
@@ -387,11 +389,7 @@ def lda_backward(x1, x2, paired, rn, dpaired, W1, want_w=True, want_dx=True):
     (dW1 (D1, D0), db1 (D1), dx1, dx2): F.normalize backward on the paired rows, then the wgrad / dgrad GEMMs."""
     lib = _lib.load()
     D1, D0 = W1.shape
-    x1, ld1 = _rows(x1, "x1", D0)
-    x2, ld2 = _rows(x2, "x2", D0)
-    if ld1 != ld2:
-        x1, x2 = x1.contiguous(), x2.contiguous()
-        ld1 = D0
+    x1, x2, ld = _pair_rows(x1, x2, D0)
     B = x1.shape[0]
     dev = x1.device
     Mp = lib.nplda_padded_dim(D1, D1)
@@ -406,7 +404,7 @@ def lda_backward(x1, x2, paired, rn, dpaired, W1, want_w=True, want_dx=True):
             wsb = lib.nplda_lda_wgrad_workspace_bytes(B, D0, D1)
             ws = torch.empty(max(wsb // 4, 4), dtype=torch.float32, device=dev)
             out = torch.empty(D1 * D0 + D1, dtype=torch.float32, device=dev)
-            _lib.check(lib.nplda_lda_wgrad_f32(_lib.ptr(x1), _lib.ptr(x2), B, ld1, _lib.ptr(du), Mp, D0, D1,
+            _lib.check(lib.nplda_lda_wgrad_f32(_lib.ptr(x1), _lib.ptr(x2), B, ld, _lib.ptr(du), Mp, D0, D1,
                                                _lib.ptr(ws), wsb, _lib.ptr(out), st), "nplda_lda_wgrad_f32")
             dW1, db1 = out[:D1 * D0].view(D1, D0), out[D1 * D0:]
         if want_dx:
@@ -427,12 +425,21 @@ def split_flat_grad(flat, D0, D1, D2):
 
 
 def _theta_array(thetas):
-    import ctypes
     arr = (ctypes.c_void_p * len(thetas))()
     for i, t in enumerate(thetas):
         _require_dev_f32(t, "theta")
         arr[i] = t.data_ptr()
     return arr
+
+
+def _step_consts(params, thetas, betas, kind):
+    """The ctypes arrays of one call -> (parr, tharr, barr, K): the six parameter pointers (None for `params` None: the
+    loss entry points take none), the K threshold pointers and the K betas (None for BCE, which has none).  Built on
+    every call: a captured graph keeps the pointers, not these arrays."""
+    K = len(thetas)
+    parr = (ctypes.c_void_p * 6)(*[q.data_ptr() for q in params]) if params is not None else None
+    barr = (ctypes.c_float * max(K, 1))(*[float(b) for b in betas]) if kind != LOSS_BCE else None
+    return parr, _theta_array(thetas), barr, K
 
 
 def loss_sums(s, t, thetas, alpha, kind):
@@ -457,7 +464,6 @@ def loss_sums(s, t, thetas, alpha, kind):
 
 def loss_finish(s, t, thetas, betas, alpha, kind, sums, want_grad=True):
     """nplda_loss_finish_f32: (loss 0-d tensor, g or None, dtheta (K,) or None)."""
-    import ctypes
     lib = _lib.load()
     s, t = s.contiguous(), t.contiguous()
     K = len(thetas)
@@ -465,9 +471,9 @@ def loss_finish(s, t, thetas, betas, alpha, kind, sums, want_grad=True):
     loss = torch.empty((), dtype=torch.float32, device=dev)
     g = torch.empty_like(s) if want_grad else None
     dth = torch.empty(K, dtype=torch.float32, device=dev) if want_grad else None
-    barr = (ctypes.c_float * max(K, 1))(*[float(b) for b in betas]) if kind != LOSS_BCE else None
+    _, tharr, barr, _ = _step_consts(None, thetas, betas, kind)
     with _lib.on_device(dev):
-        code = lib.nplda_loss_finish_f32(_lib.ptr(s), _lib.ptr(t), s.shape[0], _theta_array(thetas), barr, K,
+        code = lib.nplda_loss_finish_f32(_lib.ptr(s), _lib.ptr(t), s.shape[0], tharr, barr, K,
                                          float(alpha), kind, _lib.ptr(sums), _lib.ptr(loss), _lib.ptr(g),
                                          _lib.ptr(dth), _lib.current_stream())
     _lib.check(code, "nplda_loss_finish_f32")
@@ -477,7 +483,6 @@ def loss_finish(s, t, thetas, betas, alpha, kind, sums, want_grad=True):
 def loss_fwd_bwd(s, t, thetas, betas, alpha, kind, want_joint=False):
     """nplda_loss_fwd_bwd_f32: (loss 0-d tensor, g, dtheta (K,), sums[, the buffer g and dtheta live in]) of an unsharded batch — both loss passes in one
     call (one launch up to 4096 pairs), bit-identical to loss_sums + loss_finish."""
-    import ctypes
     lib = _lib.load()
     _require_dev_f32(s, "output")
     _require_dev_f32(t, "target")
@@ -496,9 +501,9 @@ def loss_fwd_bwd(s, t, thetas, betas, alpha, kind, want_joint=False):
     B = s.shape[0]
     joint = torch.empty(((B + 3) & ~3) + K, dtype=torch.float32, device=dev)
     g, dth = loss_joint_views(joint, B, K)
-    barr = (ctypes.c_float * max(K, 1))(*[float(b) for b in betas]) if kind != LOSS_BCE else None
+    _, tharr, barr, _ = _step_consts(None, thetas, betas, kind)
     with _lib.on_device(dev):
-        code = lib.nplda_loss_fwd_bwd_f32(_lib.ptr(s), _lib.ptr(t), s.shape[0], _theta_array(thetas), barr, K,
+        code = lib.nplda_loss_fwd_bwd_f32(_lib.ptr(s), _lib.ptr(t), s.shape[0], tharr, barr, K,
                                           float(alpha), kind, _lib.ptr(sums), _lib.ptr(loss), _lib.ptr(g),
                                           _lib.ptr(dth), _lib.current_stream())
     _lib.check(code, "nplda_loss_fwd_bwd_f32")
@@ -529,13 +534,12 @@ def repack_params(packed, keys):
     """The image of `packed` refreshed from six parameter tensors that were validated when it was first packed (same
     storage, same device: `keys` = their (data_ptr, version, device) triples) — the raw launch, nothing else."""
     lib = _lib.load()
-    b3 = packed.precision == "bf16x3"
-    fn = lib.nplda_pack_params_bf16x3 if b3 else lib.nplda_pack_params_f32
+    name = "nplda_pack_params_bf16x3" if packed.precision == "bf16x3" else "nplda_pack_params_f32"
     dev = keys[0][2]
     with _lib.on_device(dev):
-        code = fn(keys[0][0], keys[1][0], keys[2][0], keys[3][0], keys[4][0], keys[5][0], packed.D0, packed.D1, packed.D2,
-                  packed.buf.data_ptr(), packed.buf.numel() * 4, _lib.current_stream())
-    _lib.check(code, "nplda_pack_params_bf16x3" if b3 else "nplda_pack_params_f32")
+        code = getattr(lib, name)(keys[0][0], keys[1][0], keys[2][0], keys[3][0], keys[4][0], keys[5][0], packed.D0, packed.D1,
+                                  packed.D2, packed.buf.data_ptr(), packed.buf.numel() * 4, _lib.current_stream())
+    _lib.check(code, name)
     return packed
 
 
@@ -550,38 +554,90 @@ def train_step_workspace(B, packed, rows=False):
     return torch.empty(n // 4, dtype=torch.float32, device=packed.buf.device)
 
 
+# The fused train-step family funnels into one C function (train_step_impl, csrc/nplda_backward.hip); its wrappers share
+# the helpers below.  Every helper is a pure function of its arguments — train.py bakes the pointers of one call into a
+# captured graph, so nothing here may be cached between calls.  What a variant does NOT check is part of what it accepts:
+# the gradient forms leave the parameter tensors unchecked, train_step_apply checks nothing but the image's precision, the
+# dx forms reject the rows and targets the other forms copy.
+
+def _aligned_target(target, strict=None):
+    """The target vector as the kernels read it — device fp32, contiguous, 16-byte aligned: a copy where it is not, or
+    with `strict` (the name of a dx form, for the message) an error."""
+    _require_dev_f32(target, "target")
+    if strict is not None:
+        if not target.is_contiguous() or target.data_ptr() % 16:
+            raise ValueError(f"{strict}: target must be contiguous and 16-byte aligned")
+        return target
+    target = target.contiguous()
+    return target.clone() if target.data_ptr() % 16 else target
+
+
+def _dx_rows(what, packed, x1, x2, dx1, dx2, target):
+    """The dx forms take x1 / x2 / dx1 / dx2 as they are (float32 or bfloat16, nothing copied) -> (B, io_bf16)."""
+    for t in (x1, x2, dx1, dx2):
+        if t.dtype != x1.dtype or t.dtype not in (torch.float32, torch.bfloat16) or not t.is_cuda:
+            raise ValueError(f"{what}: x1, x2, dx1, dx2 must be device tensors, all float32 or all bfloat16")
+        if t.dim() != 2 or t.shape[1] != packed.D0 or t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
+            raise ValueError(f"{what}: (B, D0) rows with unit inner stride, 16-byte aligned")
+    B = x1.shape[0]
+    if x2.shape[0] != B or target.shape[0] != B or dx1.shape[0] != B or dx2.shape[0] != B:
+        raise ValueError("x1, x2, target, dx1, dx2 must have the same number of rows")
+    if x1.stride(0) != x2.stride(0) or dx1.stride(0) != dx2.stride(0):
+        raise ValueError(f"{what}: x1 / x2 (and dx1 / dx2) must share their row stride")
+    return B, 1 if x1.dtype == torch.bfloat16 else 0
+
+
+def _index_rows(rows1, rows2, target, dev):
+    """The rows forms' index vectors: int64 on the table's device, as long as the target -> (rows1, rows2, B)."""
+    if rows1.dtype != torch.int64 or rows2.dtype != torch.int64 or rows1.device != dev or rows2.device != dev:
+        raise TypeError("rows must be int64 tensors on the table's device")
+    rows1, rows2 = rows1.contiguous(), rows2.contiguous()
+    B = rows1.shape[0]
+    if rows2.shape[0] != B or target.shape[0] != B:
+        raise ValueError("rows1, rows2 and target must have the same length")
+    return rows1, rows2, B
+
+
+def _check_global_counts(global_counts):
+    if global_counts is not None and (global_counts.dtype != torch.float64 or not global_counts.is_cuda
+                                      or global_counts.numel() != 2 or not global_counts.is_contiguous()):
+        raise ValueError("global_counts must be a contiguous device float64 tensor [N_t, N_n]")
+
+
+def _check_flat(flat, packed):
+    if flat.dtype != torch.float32 or not flat.is_cuda or flat.numel() < train_step_flat_floats(packed) or not flat.is_contiguous():
+        raise ValueError("flat must be a contiguous device float32 tensor of train_step_flat_floats(packed) elements")
+
+
+def _check_inplace_params(params, thetas, what):
+    for q in list(params) + list(thetas):
+        _require_dev_f32(q, "parameter")
+        if not q.is_contiguous():
+            raise ValueError(f"{what} updates the parameter tensors in place: they must be contiguous")
+
+
+def _floats(*values):
+    return [float(v) for v in values]
+
+
 def train_step(x1, x2, target, params, thetas, betas, alpha, kind, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps,
                weight_decay, packed, ws, loss, grad_out=None, loss_sum=None):
     """nplda_train_step_f32: forward -> loss -> backward -> Adam on `params` (the six parameter tensors, updated IN
     PLACE) and `thetas`, `packed` refreshed to the updated parameters, `loss` (0-d device tensor) written; `loss_sum` (optional 1-element fp64 device tensor) += loss.  Three launches."""
-    import ctypes
     lib = _lib.load()
     _need_fp32(packed, "train_step")
-    x1, ld1 = _rows(x1, "x1", packed.D0)
-    x2, ld2 = _rows(x2, "x2", packed.D0)
+    x1, x2, ld = _pair_rows(x1, x2, packed.D0)
     if x1.shape[0] != x2.shape[0] or target.shape[0] != x1.shape[0]:
         raise ValueError("x1, x2 and target must have the same number of rows")
-    if ld1 != ld2:
-        x1, x2 = x1.contiguous(), x2.contiguous()
-        ld1 = ld2 = packed.D0
-    _require_dev_f32(target, "target")
-    target = target.contiguous()
-    if target.data_ptr() % 16:
-        target = target.clone()
-    for q in list(params) + list(thetas):
-        _require_dev_f32(q, "parameter")
-        if not q.is_contiguous():
-            raise ValueError("train_step updates the parameter tensors in place: they must be contiguous")
-    K = len(thetas)
-    parr = (ctypes.c_void_p * 6)(*[q.data_ptr() for q in params])
-    barr = (ctypes.c_float * max(K, 1))(*[float(b) for b in betas]) if kind != LOSS_BCE else None
+    target = _aligned_target(target)
+    _check_inplace_params(params, thetas, "train_step")
+    parr, tharr, barr, K = _step_consts(params, thetas, betas, kind)
     with _lib.on_device(x1.device):
-        code = lib.nplda_train_step_f32(_lib.ptr(x1), _lib.ptr(x2), x1.shape[0], ld1, _lib.ptr(target), parr, packed.D0,
-                                        packed.D1, packed.D2, _theta_array(thetas), barr, K, float(alpha), kind,
-                                        _lib.ptr(exp_avg), _lib.ptr(exp_avg_sq), _lib.ptr(step), float(lr), float(beta1),
-                                        float(beta2), float(eps), float(weight_decay), _lib.ptr(packed.buf), _lib.ptr(ws),
-                                        ws.numel() * 4, _lib.ptr(loss), _lib.ptr(loss_sum) if loss_sum is not None else None,
-                                        _lib.ptr(grad_out) if grad_out is not None else None, _lib.current_stream())
+        code = lib.nplda_train_step_f32(_lib.ptr(x1), _lib.ptr(x2), x1.shape[0], ld, _lib.ptr(target), parr, packed.D0,
+                                        packed.D1, packed.D2, tharr, barr, K, float(alpha), kind, _lib.ptr(exp_avg),
+                                        _lib.ptr(exp_avg_sq), _lib.ptr(step), *_floats(lr, beta1, beta2, eps, weight_decay),
+                                        _lib.ptr(packed.buf), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(loss),
+                                        _lib.ptr(loss_sum), _lib.ptr(grad_out), _lib.current_stream())
     _lib.check(code, "nplda_train_step_f32")
     return loss
 
@@ -595,34 +651,20 @@ def train_step_grad(x1, x2, target, params, thetas, betas, alpha, kind, step, pa
     """nplda_train_step_grad_f32: this rank's share of a data-parallel step up to the flat gradient (+ loss sums) in
     `flat`; `global_counts` = device float64 [N_t, N_n] of the GLOBAL minibatch (None: one rank).  Follow with a SUM
     all-reduce of `flat` and train_step_apply."""
-    import ctypes
     lib = _lib.load()
     _need_fp32(packed, "train_step_grad")
-    x1, ld1 = _rows(x1, "x1", packed.D0)
-    x2, ld2 = _rows(x2, "x2", packed.D0)
+    x1, x2, ld = _pair_rows(x1, x2, packed.D0)
     if x1.shape[0] != x2.shape[0] or target.shape[0] != x1.shape[0]:
         raise ValueError("x1, x2 and target must have the same number of rows")
-    if ld1 != ld2:
-        x1, x2 = x1.contiguous(), x2.contiguous()
-        ld1 = ld2 = packed.D0
-    _require_dev_f32(target, "target")
-    target = target.contiguous()
-    if target.data_ptr() % 16:
-        target = target.clone()
-    if global_counts is not None and (global_counts.dtype != torch.float64 or not global_counts.is_cuda
-                                      or global_counts.numel() != 2 or not global_counts.is_contiguous()):
-        raise ValueError("global_counts must be a contiguous device float64 tensor [N_t, N_n]")
-    if flat.dtype != torch.float32 or not flat.is_cuda or flat.numel() < train_step_flat_floats(packed) or not flat.is_contiguous():
-        raise ValueError("flat must be a contiguous device float32 tensor of train_step_flat_floats(packed) elements")
-    K = len(thetas)
-    parr = (ctypes.c_void_p * 6)(*[q.data_ptr() for q in params])
-    barr = (ctypes.c_float * max(K, 1))(*[float(b) for b in betas]) if kind != LOSS_BCE else None
+    target = _aligned_target(target)
+    _check_global_counts(global_counts)
+    _check_flat(flat, packed)
+    parr, tharr, barr, K = _step_consts(params, thetas, betas, kind)
     with _lib.on_device(x1.device):
-        code = lib.nplda_train_step_grad_f32(_lib.ptr(x1), _lib.ptr(x2), x1.shape[0], ld1, _lib.ptr(target),
-                                             _lib.ptr(global_counts) if global_counts is not None else None, parr,
-                                             packed.D0, packed.D1, packed.D2, _theta_array(thetas), barr, K, float(alpha),
-                                             kind, _lib.ptr(step), _lib.ptr(packed.buf), _lib.ptr(ws), ws.numel() * 4,
-                                             _lib.ptr(flat), _lib.current_stream())
+        code = lib.nplda_train_step_grad_f32(_lib.ptr(x1), _lib.ptr(x2), x1.shape[0], ld, _lib.ptr(target),
+                                             _lib.ptr(global_counts), parr, packed.D0, packed.D1, packed.D2, tharr, barr, K,
+                                             float(alpha), kind, _lib.ptr(step), _lib.ptr(packed.buf), _lib.ptr(ws),
+                                             ws.numel() * 4, _lib.ptr(flat), _lib.current_stream())
     _lib.check(code, "nplda_train_step_grad_f32")
     return flat
 
@@ -631,35 +673,20 @@ def train_step_grad_rows(table, rows1, rows2, target, params, thetas, betas, alp
                          global_counts=None):
     """nplda_train_step_grad_rows_f32: train_step_grad on the pairs (table[rows1], table[rows2]); the first kernel gathers
     the rows itself.  `ws`: train_step_workspace(B, packed, rows=True)."""
-    import ctypes
     lib = _lib.load()
     _need_fp32(packed, "train_step_grad_rows")
     table, ldt = _rows(table, "table", packed.D0)
-    dev = table.device
-    if rows1.dtype != torch.int64 or rows2.dtype != torch.int64 or rows1.device != dev or rows2.device != dev:
-        raise TypeError("rows must be int64 tensors on the table's device")
-    rows1, rows2 = rows1.contiguous(), rows2.contiguous()
-    B = rows1.shape[0]
-    if rows2.shape[0] != B or target.shape[0] != B:
-        raise ValueError("rows1, rows2 and target must have the same length")
-    _require_dev_f32(target, "target")
-    target = target.contiguous()
-    if target.data_ptr() % 16:
-        target = target.clone()
-    if global_counts is not None and (global_counts.dtype != torch.float64 or not global_counts.is_cuda
-                                      or global_counts.numel() != 2 or not global_counts.is_contiguous()):
-        raise ValueError("global_counts must be a contiguous device float64 tensor [N_t, N_n]")
-    if flat.dtype != torch.float32 or not flat.is_cuda or flat.numel() < train_step_flat_floats(packed) or not flat.is_contiguous():
-        raise ValueError("flat must be a contiguous device float32 tensor of train_step_flat_floats(packed) elements")
-    K = len(thetas)
-    parr = (ctypes.c_void_p * 6)(*[q.data_ptr() for q in params])
-    barr = (ctypes.c_float * max(K, 1))(*[float(b) for b in betas]) if kind != LOSS_BCE else None
-    with _lib.on_device(dev):
+    rows1, rows2, B = _index_rows(rows1, rows2, target, table.device)
+    target = _aligned_target(target)
+    _check_global_counts(global_counts)
+    _check_flat(flat, packed)
+    parr, tharr, barr, K = _step_consts(params, thetas, betas, kind)
+    with _lib.on_device(table.device):
         code = lib.nplda_train_step_grad_rows_f32(_lib.ptr(table), table.shape[0], ldt, _lib.ptr(rows1), _lib.ptr(rows2), B,
-                                                  _lib.ptr(target), _lib.ptr(global_counts) if global_counts is not None else None,
-                                                  parr, packed.D0, packed.D1, packed.D2, _theta_array(thetas), barr, K,
-                                                  float(alpha), kind, _lib.ptr(step), _lib.ptr(packed.buf), _lib.ptr(ws),
-                                                  ws.numel() * 4, _lib.ptr(flat), _lib.current_stream())
+                                                  _lib.ptr(target), _lib.ptr(global_counts), parr, packed.D0, packed.D1,
+                                                  packed.D2, tharr, barr, K, float(alpha), kind, _lib.ptr(step),
+                                                  _lib.ptr(packed.buf), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(flat),
+                                                  _lib.current_stream())
     _lib.check(code, "nplda_train_step_grad_rows_f32")
     return flat
 
@@ -668,37 +695,18 @@ def train_step_grad_dx(x1, x2, target, params, thetas, betas, alpha, kind, step,
                        global_counts=None):
     """nplda_train_step_grad_dx_f32: train_step_grad that also writes dL/dx1, dL/dx2 (float32 or bfloat16, as x1 / x2) — the
     data-parallel form of train_step_dx's first half.  `ws`: train_step_dx_workspace."""
-    import ctypes
     lib = _lib.load()
     _need_fp32(packed, "train_step_grad_dx")
-    bf = x1.dtype == torch.bfloat16
-    for t in (x1, x2, dx1, dx2):
-        if t.dtype != x1.dtype or t.dtype not in (torch.float32, torch.bfloat16) or not t.is_cuda:
-            raise ValueError("train_step_grad_dx: x1, x2, dx1, dx2 must be device tensors, all float32 or all bfloat16")
-        if t.dim() != 2 or t.shape[1] != packed.D0 or t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
-            raise ValueError("train_step_grad_dx: (B, D0) rows with unit inner stride, 16-byte aligned")
-    B = x1.shape[0]
-    if x2.shape[0] != B or target.shape[0] != B or dx1.shape[0] != B or dx2.shape[0] != B:
-        raise ValueError("x1, x2, target, dx1, dx2 must have the same number of rows")
-    if x1.stride(0) != x2.stride(0) or dx1.stride(0) != dx2.stride(0):
-        raise ValueError("train_step_grad_dx: x1 / x2 (and dx1 / dx2) must share their row stride")
-    _require_dev_f32(target, "target")
-    if not target.is_contiguous() or target.data_ptr() % 16:
-        raise ValueError("train_step_grad_dx: target must be contiguous and 16-byte aligned")
-    if global_counts is not None and (global_counts.dtype != torch.float64 or not global_counts.is_cuda
-                                      or global_counts.numel() != 2 or not global_counts.is_contiguous()):
-        raise ValueError("global_counts must be a contiguous device float64 tensor [N_t, N_n]")
-    if flat.dtype != torch.float32 or not flat.is_cuda or flat.numel() < train_step_flat_floats(packed) or not flat.is_contiguous():
-        raise ValueError("flat must be a contiguous device float32 tensor of train_step_flat_floats(packed) elements")
-    K = len(thetas)
-    parr = (ctypes.c_void_p * 6)(*[q.data_ptr() for q in params])
-    barr = (ctypes.c_float * max(K, 1))(*[float(b) for b in betas]) if kind != LOSS_BCE else None
+    B, bf = _dx_rows("train_step_grad_dx", packed, x1, x2, dx1, dx2, target)
+    target = _aligned_target(target, strict="train_step_grad_dx")
+    _check_global_counts(global_counts)
+    _check_flat(flat, packed)
+    parr, tharr, barr, K = _step_consts(params, thetas, betas, kind)
     with _lib.on_device(x1.device):
-        code = lib.nplda_train_step_grad_dx_f32(x1.data_ptr(), x2.data_ptr(), B, x1.stride(0), 1 if bf else 0, _lib.ptr(target),
-                                                _lib.ptr(global_counts) if global_counts is not None else None, parr,
-                                                packed.D0, packed.D1, packed.D2, _theta_array(thetas), barr, K, float(alpha),
-                                                kind, _lib.ptr(step), _lib.ptr(packed.buf), _lib.ptr(ws), ws.numel() * 4,
-                                                _lib.ptr(flat), dx1.data_ptr(), dx2.data_ptr(), dx1.stride(0),
+        code = lib.nplda_train_step_grad_dx_f32(x1.data_ptr(), x2.data_ptr(), B, x1.stride(0), bf, _lib.ptr(target),
+                                                _lib.ptr(global_counts), parr, packed.D0, packed.D1, packed.D2, tharr, barr, K,
+                                                float(alpha), kind, _lib.ptr(step), _lib.ptr(packed.buf), _lib.ptr(ws),
+                                                ws.numel() * 4, _lib.ptr(flat), dx1.data_ptr(), dx2.data_ptr(), dx1.stride(0),
                                                 _lib.current_stream())
     _lib.check(code, "nplda_train_step_grad_dx_f32")
     return flat
@@ -707,18 +715,14 @@ def train_step_grad_dx(x1, x2, target, params, thetas, betas, alpha, kind, step,
 def train_step_apply(flat, params, thetas, betas, alpha, kind, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps,
                      weight_decay, packed, loss, loss_sum=None):
     """nplda_train_step_apply_f32: the update half of the data-parallel step from the all-reduced `flat`."""
-    import ctypes
     lib = _lib.load()
     _need_fp32(packed, "train_step_apply")
-    K = len(thetas)
-    parr = (ctypes.c_void_p * 6)(*[q.data_ptr() for q in params])
-    barr = (ctypes.c_float * max(K, 1))(*[float(b) for b in betas]) if kind != LOSS_BCE else None
+    parr, tharr, barr, K = _step_consts(params, thetas, betas, kind)
     with _lib.on_device(flat.device):
-        code = lib.nplda_train_step_apply_f32(_lib.ptr(flat), parr, packed.D0, packed.D1, packed.D2, _theta_array(thetas),
-                                              barr, K, float(alpha), kind, _lib.ptr(exp_avg), _lib.ptr(exp_avg_sq),
-                                              _lib.ptr(step), float(lr), float(beta1), float(beta2), float(eps),
-                                              float(weight_decay), _lib.ptr(packed.buf), _lib.ptr(loss),
-                                              _lib.ptr(loss_sum) if loss_sum is not None else None, _lib.current_stream())
+        code = lib.nplda_train_step_apply_f32(_lib.ptr(flat), parr, packed.D0, packed.D1, packed.D2, tharr, barr, K,
+                                              float(alpha), kind, _lib.ptr(exp_avg), _lib.ptr(exp_avg_sq), _lib.ptr(step),
+                                              *_floats(lr, beta1, beta2, eps, weight_decay), _lib.ptr(packed.buf),
+                                              _lib.ptr(loss), _lib.ptr(loss_sum), _lib.current_stream())
     _lib.check(code, "nplda_train_step_apply_f32")
     return loss
 
@@ -728,37 +732,19 @@ def train_step_dx(x1, x2, target, params, thetas, betas, alpha, kind, exp_avg, e
     """nplda_train_step_dx_f32: train_step that also writes dL/dx1, dL/dx2 into `dx1`, `dx2` (B, D0).  x1 / x2 and dx1 / dx2
     are all float32 or all bfloat16 (the head's arithmetic is fp32 either way).  Four launches.  `ws`: a float32 tensor of
     nplda_train_step_dx_workspace_bytes (train_step_dx_workspace)."""
-    import ctypes
     lib = _lib.load()
     _need_fp32(packed, "train_step_dx")
-    bf = x1.dtype == torch.bfloat16
-    for t in (x1, x2, dx1, dx2):
-        if t.dtype != x1.dtype or t.dtype not in (torch.float32, torch.bfloat16) or not t.is_cuda:
-            raise ValueError("train_step_dx: x1, x2, dx1, dx2 must be device tensors, all float32 or all bfloat16")
-        if t.dim() != 2 or t.shape[1] != packed.D0 or t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
-            raise ValueError("train_step_dx: (B, D0) rows with unit inner stride, 16-byte aligned")
-    B = x1.shape[0]
-    if x2.shape[0] != B or target.shape[0] != B or dx1.shape[0] != B or dx2.shape[0] != B:
-        raise ValueError("x1, x2, target, dx1, dx2 must have the same number of rows")
-    if x1.stride(0) != x2.stride(0) or dx1.stride(0) != dx2.stride(0):
-        raise ValueError("train_step_dx: x1 / x2 (and dx1 / dx2) must share their row stride")
-    _require_dev_f32(target, "target")
-    if not target.is_contiguous() or target.data_ptr() % 16:
-        raise ValueError("train_step_dx: target must be contiguous and 16-byte aligned")
-    for q in list(params) + list(thetas):
-        _require_dev_f32(q, "parameter")
-        if not q.is_contiguous():
-            raise ValueError("train_step_dx updates the parameter tensors in place: they must be contiguous")
-    K = len(thetas)
-    parr = (ctypes.c_void_p * 6)(*[q.data_ptr() for q in params])
-    barr = (ctypes.c_float * max(K, 1))(*[float(b) for b in betas]) if kind != LOSS_BCE else None
+    B, bf = _dx_rows("train_step_dx", packed, x1, x2, dx1, dx2, target)
+    target = _aligned_target(target, strict="train_step_dx")
+    _check_inplace_params(params, thetas, "train_step_dx")
+    parr, tharr, barr, K = _step_consts(params, thetas, betas, kind)
     with _lib.on_device(x1.device):
-        code = lib.nplda_train_step_dx_f32(_lib.ptr(x1), _lib.ptr(x2), B, x1.stride(0), 1 if bf else 0, _lib.ptr(target), parr,
-                                           packed.D0, packed.D1, packed.D2, _theta_array(thetas), barr, K, float(alpha), kind,
-                                           _lib.ptr(exp_avg), _lib.ptr(exp_avg_sq), _lib.ptr(step), float(lr), float(beta1),
-                                           float(beta2), float(eps), float(weight_decay), _lib.ptr(packed.buf), _lib.ptr(ws),
-                                           ws.numel() * 4, _lib.ptr(loss), _lib.ptr(loss_sum) if loss_sum is not None else None,
-                                           None, _lib.ptr(dx1), _lib.ptr(dx2), dx1.stride(0), _lib.current_stream())
+        code = lib.nplda_train_step_dx_f32(_lib.ptr(x1), _lib.ptr(x2), B, x1.stride(0), bf, _lib.ptr(target), parr, packed.D0,
+                                           packed.D1, packed.D2, tharr, barr, K, float(alpha), kind, _lib.ptr(exp_avg),
+                                           _lib.ptr(exp_avg_sq), _lib.ptr(step), *_floats(lr, beta1, beta2, eps, weight_decay),
+                                           _lib.ptr(packed.buf), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(loss),
+                                           _lib.ptr(loss_sum), None, _lib.ptr(dx1), _lib.ptr(dx2), dx1.stride(0),
+                                           _lib.current_stream())
     _lib.check(code, "nplda_train_step_dx_f32")
     return loss
 
@@ -775,36 +761,19 @@ def train_step_rows(table, rows1, rows2, target, params, thetas, betas, alpha, k
                     beta2, eps, weight_decay, packed, ws, loss, grad_out=None, loss_sum=None):
     """nplda_train_step_rows_f32: train_step on the pairs (table[rows1], table[rows2]) of a resident x-vector matrix; the
     first kernel gathers the rows itself.  rows1 / rows2: int64 device tensors with values in [0, len(table))."""
-    import ctypes
     lib = _lib.load()
     _need_fp32(packed, "train_step_rows")
     table, ldt = _rows(table, "table", packed.D0)
-    dev = table.device
-    if rows1.dtype != torch.int64 or rows2.dtype != torch.int64 or rows1.device != dev or rows2.device != dev:
-        raise TypeError("rows must be int64 tensors on the table's device")
-    rows1, rows2 = rows1.contiguous(), rows2.contiguous()
-    B = rows1.shape[0]
-    if rows2.shape[0] != B or target.shape[0] != B:
-        raise ValueError("rows1, rows2 and target must have the same length")
-    _require_dev_f32(target, "target")
-    target = target.contiguous()
-    if target.data_ptr() % 16:
-        target = target.clone()
-    for q in list(params) + list(thetas):
-        _require_dev_f32(q, "parameter")
-        if not q.is_contiguous():
-            raise ValueError("train_step updates the parameter tensors in place: they must be contiguous")
-    K = len(thetas)
-    parr = (ctypes.c_void_p * 6)(*[q.data_ptr() for q in params])
-    barr = (ctypes.c_float * max(K, 1))(*[float(b) for b in betas]) if kind != LOSS_BCE else None
-    with _lib.on_device(dev):
+    rows1, rows2, B = _index_rows(rows1, rows2, target, table.device)
+    target = _aligned_target(target)
+    _check_inplace_params(params, thetas, "train_step")
+    parr, tharr, barr, K = _step_consts(params, thetas, betas, kind)
+    with _lib.on_device(table.device):
         code = lib.nplda_train_step_rows_f32(_lib.ptr(table), table.shape[0], ldt, _lib.ptr(rows1), _lib.ptr(rows2), B,
-                                             _lib.ptr(target), parr, packed.D0, packed.D1, packed.D2, _theta_array(thetas),
-                                             barr, K, float(alpha), kind, _lib.ptr(exp_avg), _lib.ptr(exp_avg_sq),
-                                             _lib.ptr(step), float(lr), float(beta1), float(beta2), float(eps),
-                                             float(weight_decay), _lib.ptr(packed.buf), _lib.ptr(ws), ws.numel() * 4,
-                                             _lib.ptr(loss), _lib.ptr(loss_sum) if loss_sum is not None else None,
-                                             _lib.ptr(grad_out) if grad_out is not None else None,
+                                             _lib.ptr(target), parr, packed.D0, packed.D1, packed.D2, tharr, barr, K,
+                                             float(alpha), kind, _lib.ptr(exp_avg), _lib.ptr(exp_avg_sq), _lib.ptr(step),
+                                             *_floats(lr, beta1, beta2, eps, weight_decay), _lib.ptr(packed.buf), _lib.ptr(ws),
+                                             ws.numel() * 4, _lib.ptr(loss), _lib.ptr(loss_sum), _lib.ptr(grad_out),
                                              _lib.current_stream())
     _lib.check(code, "nplda_train_step_rows_f32")
     return loss
@@ -815,7 +784,6 @@ def train_step_records(table, cursor, stage, B, params, thetas, betas, alpha, ki
     """nplda_train_step_records_f32: train_step_rows on the record in `stage` (uint8 device tensor of 20 B bytes:
     [rows1 (B int64) | rows2 (B int64) | labels (B float32)]); the step's last kernel copies the epoch's next record there
     (cursor: int64 device tensor [address of record 0, next record to stage, record count])."""
-    import ctypes
     lib = _lib.load()
     _need_fp32(packed, "train_step_records")
     table, ldt = _rows(table, "table", packed.D0)
@@ -823,21 +791,15 @@ def train_step_records(table, cursor, stage, B, params, thetas, betas, alpha, ki
         raise TypeError("cursor must be a contiguous int64 tensor of 3 elements on the table's device")
     if stage.dtype != torch.uint8 or stage.device != table.device or stage.numel() != 20 * int(B) or not stage.is_contiguous():
         raise TypeError("stage must be a contiguous uint8 tensor of 20 B bytes on the table's device")
-    for q in list(params) + list(thetas):
-        _require_dev_f32(q, "parameter")
-        if not q.is_contiguous():
-            raise ValueError("train_step updates the parameter tensors in place: they must be contiguous")
-    K = len(thetas)
-    parr = (ctypes.c_void_p * 6)(*[q.data_ptr() for q in params])
-    barr = (ctypes.c_float * max(K, 1))(*[float(b) for b in betas]) if kind != LOSS_BCE else None
+    _check_inplace_params(params, thetas, "train_step")
+    parr, tharr, barr, K = _step_consts(params, thetas, betas, kind)
     with _lib.on_device(table.device):
-        code = lib.nplda_train_step_records_f32(_lib.ptr(table), table.shape[0], ldt, _lib.ptr(cursor), _lib.ptr(stage), int(B), parr,
-                                                packed.D0, packed.D1, packed.D2, _theta_array(thetas), barr, K,
-                                                float(alpha), kind, _lib.ptr(exp_avg), _lib.ptr(exp_avg_sq), _lib.ptr(step),
-                                                float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
-                                                _lib.ptr(packed.buf), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(loss),
-                                                _lib.ptr(loss_sum) if loss_sum is not None else None,
-                                                _lib.ptr(grad_out) if grad_out is not None else None, _lib.current_stream())
+        code = lib.nplda_train_step_records_f32(_lib.ptr(table), table.shape[0], ldt, _lib.ptr(cursor), _lib.ptr(stage), int(B),
+                                                parr, packed.D0, packed.D1, packed.D2, tharr, barr, K, float(alpha), kind,
+                                                _lib.ptr(exp_avg), _lib.ptr(exp_avg_sq), _lib.ptr(step),
+                                                *_floats(lr, beta1, beta2, eps, weight_decay), _lib.ptr(packed.buf),
+                                                _lib.ptr(ws), ws.numel() * 4, _lib.ptr(loss), _lib.ptr(loss_sum),
+                                                _lib.ptr(grad_out), _lib.current_stream())
     _lib.check(code, "nplda_train_step_records_f32")
     return loss
 
@@ -1176,20 +1138,16 @@ def gb_pack(W1, b1, mu_t, Lam_t, mu_n, Lam_n):
 def _gb_call(x1, x2, packed, want_s, want_paired, want_rn=False):
     lib = _lib.load()
     buf, D0, D1 = packed
-    x1, ld1 = _rows(x1, "x1", D0)
-    x2, ld2 = _rows(x2, "x2", D0)
+    x1, x2, ld = _pair_rows(x1, x2, D0)
     if x1.shape[0] != x2.shape[0]:
         raise ValueError("x1 and x2 must have the same number of rows")
-    if ld1 != ld2:
-        x1, x2 = x1.contiguous(), x2.contiguous()
-        ld1 = ld2 = D0
     B = x1.shape[0]
     s = torch.empty(B, dtype=torch.float32, device=x1.device) if want_s else None
     paired = torch.empty((B, 2 * D1), dtype=torch.float32, device=x1.device) if want_paired else None
     rn = torch.empty(2 * B, dtype=torch.float32, device=x1.device) if want_rn else None
     if B > 0:
         with _lib.on_device(x1.device):
-            code = lib.gb_score_pairs_ex_f32(_lib.ptr(x1), _lib.ptr(x2), B, ld1, _lib.ptr(buf), D0, D1, _lib.ptr(s),
+            code = lib.gb_score_pairs_ex_f32(_lib.ptr(x1), _lib.ptr(x2), B, ld, _lib.ptr(buf), D0, D1, _lib.ptr(s),
                                              _lib.ptr(paired), _lib.ptr(rn), _lib.current_stream())
         _lib.check(code, "gb_score_pairs_ex_f32")
     return (s, paired, rn) if want_rn else (s, paired)
@@ -1264,18 +1222,14 @@ def quadform_score_rows(y1, y2, packed):
     """gb_score_rows_f32: like quadform_score_pairs with the normalisation step skipped."""
     lib = _lib.load()
     buf, D0, D1 = packed
-    y1, ld1 = _rows(y1, "y1", D0)
-    y2, ld2 = _rows(y2, "y2", D0)
+    y1, y2, ld = _pair_rows(y1, y2, D0, "y1", "y2")
     if y1.shape[0] != y2.shape[0]:
         raise ValueError("y1 and y2 must have the same number of rows")
-    if ld1 != ld2:
-        y1, y2 = y1.contiguous(), y2.contiguous()
-        ld1 = ld2 = D0
     B = y1.shape[0]
     s = torch.empty(B, dtype=torch.float32, device=y1.device)
     if B > 0:
         with _lib.on_device(y1.device):
-            code = lib.gb_score_rows_f32(_lib.ptr(y1), _lib.ptr(y2), B, ld1, _lib.ptr(buf), D0, D1, _lib.ptr(s),
+            code = lib.gb_score_rows_f32(_lib.ptr(y1), _lib.ptr(y2), B, ld, _lib.ptr(buf), D0, D1, _lib.ptr(s),
                                          _lib.current_stream())
         _lib.check(code, "gb_score_rows_f32")
     return s
@@ -1345,7 +1299,6 @@ def dplda_update(paired, g, wlr, blr, m, v, step, lr, beta1, beta2, eps, wd, the
     parameter and into `image` (the (buf, D0, D1) of dplda_pack the next forward scores with).  m / v: flat moments
     [weight | bias | thresholds]; step: device [steps taken, scratch].  loss / loss_sum: optional 0-d float32 / (1,) float64
     device tensors, loss_sum += loss inside the update launch."""
-    import ctypes
     lib = _lib.load()
     B, n = paired.shape
     if loss_sum is not None and (loss is None or loss.dtype != torch.float32 or loss_sum.dtype != torch.float64):
@@ -1379,7 +1332,6 @@ def dplda_update_loss(paired, s, t, loss_thetas, betas, alpha, kind, wlr, blr, m
     """nplda_dplda_update_loss_f32: dplda_update with the loss inside its first launch — the moments blocks form dL/ds_i from
     (s, t) themselves, one more block of that launch is the loss kernel (loss, dL/dtheta).  Returns (loss, dtheta, ws), or None
     when the batch is outside the one-block loss (B > 4096 / unaligned): the caller runs loss_fwd_bwd + dplda_update."""
-    import ctypes
     lib = _lib.load()
     B, n = paired.shape
     D1 = n // 2
@@ -1491,7 +1443,6 @@ def detcost_sweep(scores, target, betas, exact=False, want_eer=False):
         raise _lib.NpldaHipError(f"{N} scores are outside the supported range")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
     out = torch.empty(2 * K + 2, dtype=torch.float32, device=s.device)
-    import ctypes
     barr = (ctypes.c_float * K)(*[float(b) for b in betas])
     base = out.data_ptr()
     with _lib.on_device(s.device):
