@@ -720,6 +720,41 @@ int nplda_feat_cmn_select_f32(const float* frames, const int64_t* offsets, int64
                               const uint8_t* mask, int cmn_window, int min_frames, float* out, int32_t* counts, void* ws,
                               size_t ws_bytes, nplda_stream_t stream);
 
+/* ---- MFCCs from 16-bit audio (compute-mfcc-feats with --dither=0) ------------------------------------------------ */
+
+/* csrc/nplda_mfcc.hip, design/k14_mfcc.md: samples -> frames -> mean removal, energy, pre-emphasis, window -> real DFT as
+ * a matrix product -> power -> mel banks -> log -> DCT and lifter, one kernel.  The three tables are built by the caller
+ * (neuralplda_amd/mfcc.py MfccPlan) in float64, rounded once and laid out in MFMA fragment order, lane = 0 .. 63,
+ * i = 0 .. 3, KB = ceil(N / 16), NBW = P / 128, MB = 2 if B <= 32 else 4, zero outside the matrices:
+ *   dft [kb][w][u][lane][i]   = t(n = 16 kb + 4 (lane >> 4) + i, bin = 16 (w NBW + u % NBW) + (lane & 15)), w = 0 .. 3,
+ *                               u = 0 .. 2 NBW - 1: t = cos(2 pi n bin / P) for u < NBW, sin for the others
+ *   bank[bb][mb][lane][i]     = weight of FFT bin 16 bb + 4 (lane >> 4) + i in mel bin 16 mb + (lane & 15), bb < P / 32
+ *   dct [kb][cb][lane][i]     = lifter(c) D(c, b) for c = 16 cb + (lane & 15), b = 16 kb + 4 (lane >> 4) + i, kb, cb < MB */
+#define NPLDA_MFCC_TILE 32         /* output frames per block */
+#define NPLDA_MFCC_REMOVE_DC  1    /* flags */
+#define NPLDA_MFCC_USE_ENERGY 2
+#define NPLDA_MFCC_RAW_ENERGY 4
+typedef struct nplda_mfcc_geometry {
+    int32_t N, P, S;        /* samples per frame, padded (power of two) frame, samples per shift */
+    int32_t snip_edges;     /* non-zero: frame f starts at f S; zero: at f S + S / 2 - N / 2, indices reflected into the utterance */
+    int32_t B, C;           /* mel bins, cepstra */
+    int32_t flags;
+    float preemph;          /* pre-emphasis coefficient */
+    float energy_floor;     /* > 0: log energy >= log of it */
+} nplda_mfcc_geometry;
+
+/* Bytes of image `which` (0 dft, 1 bank, 2 dct) for a supported geometry, 0 otherwise. */
+size_t nplda_mfcc_image_bytes(const nplda_mfcc_geometry* geometry, int which);
+/* out (total_frames, C) float32 = the MFCCs of n_utts utterances, one launch whatever their lengths.  samples: DEVICE int16,
+ * utterance u at [sample_offsets[u], sample_offsets[u + 1]); frame_offsets: its rows of `out` (both DEVICE int64 arrays of
+ * n_utts + 1; the caller computes the frame counts on the host, so nothing is read back).  geometry: HOST pointer.  window:
+ * N floats; images: 16-byte aligned.  Supported: N % 4 == 0, N <= 512, P in {256, 512}, N <= P, B <= 64, C <= B — anything
+ * else returns NPLDA_EUNSUPPORTED before any launch.  total_frames == 0 is a no-op.  Nothing outside an utterance's own
+ * samples is read; same bits on every call; a frame's row does not depend on the batch. */
+int nplda_mfcc_frames_f32(const int16_t* samples, const int64_t* sample_offsets, const int64_t* frame_offsets, int64_t n_utts,
+                          int64_t total_frames, const nplda_mfcc_geometry* geometry, const float* window, const void* dft_image,
+                          const void* bank_image, const void* dct_image, float* out, nplda_stream_t stream);
+
 /* ---- measurement utility ------------------------------------------------------------------------------------- */
 
 /* Shader-clock probe for bench.py (no reference counterpart): one wave that stays resident for window_us microseconds

@@ -20,7 +20,7 @@ import torch
 
 from . import _lib, kaldi_format
 
-__all__ = ["VadOptions", "PreparedFeatures", "prepare_features", "decode_features", "energy_vad", "cmn_select", "FEAT_DIM"]
+__all__ = ["VadOptions", "PreparedFeatures", "prepare_features", "prepare_frames", "decode_features", "energy_vad", "cmn_select", "FEAT_DIM"]
 
 FEAT_DIM = 30  # include/nplda_hip.h NPLDA_FEAT_DIM
 
@@ -187,13 +187,10 @@ def cmn_select(frames, lengths, mask=None, cmn_window=300, min_frames=25):
     return out[:int(cnt[cnt >= int(min_frames)].sum())], cnt
 
 
-def prepare_features(feats, vad=VadOptions(), cmn_window=300, min_frames=25, device=None):
-    """feats: what kaldi_format.load_feature_scp returned.  vad: VadOptions (energy VAD on c0, on the device), a {key: 0/1
-    vector} dict or the path of a vad.scp (given decisions), or None (every frame is kept).  cmn_window: frames of the
-    centred sliding mean (0: none).  Utterances with fewer than min_frames voiced frames are left out and returned in
-    `dropped` with their counts.  One host synchronisation (the voiced counts).  -> PreparedFeatures."""
-    keys = list(feats[0])
-    frames, lengths = decode_features(feats, device)
+def prepare_frames(keys, frames, lengths, vad=VadOptions(), cmn_window=300, min_frames=25):
+    """The part of prepare_features after the decode, for frames that are on the device already (mfcc.compute_mfcc):
+    keys, frames (sum T_u, 30) and [T_u] -> PreparedFeatures.  vad, cmn_window, min_frames: as prepare_features."""
+    keys = list(keys)
     if not keys:
         return PreparedFeatures(frames, [], [], [])
     if vad is None:
@@ -207,3 +204,12 @@ def prepare_features(feats, vad=VadOptions(), cmn_window=300, min_frames=25, dev
     keep = cnt >= int(min_frames)
     return PreparedFeatures(out, [int(c) for c in cnt[keep]], [k for k, f in zip(keys, keep) if f],
                             [(k, int(c)) for k, c, f in zip(keys, cnt, keep) if not f])
+
+
+def prepare_features(feats, vad=VadOptions(), cmn_window=300, min_frames=25, device=None):
+    """feats: what kaldi_format.load_feature_scp returned.  vad: VadOptions (energy VAD on c0, on the device), a {key: 0/1
+    vector} dict or the path of a vad.scp (given decisions), or None (every frame is kept).  cmn_window: frames of the
+    centred sliding mean (0: none).  Utterances with fewer than min_frames voiced frames are left out and returned in
+    `dropped` with their counts.  One host synchronisation (the voiced counts).  -> PreparedFeatures."""
+    frames, lengths = decode_features(feats, device)
+    return prepare_frames(feats[0], frames, lengths, vad, cmn_window, min_frames)

@@ -9,6 +9,9 @@ installation is needed.  It is host-side file I/O only.
 Feature matrices (`feats.scp` of a Kaldi data directory) are read too, including the compressed forms `CM` / `CM2` / `CM3`
 that `make_mfcc.sh` writes by default: `read_matrix` decodes one on the host, `load_feature_scp` collects the raw bodies of
 many into one buffer for the device decoder (neuralplda_amd/features.py, design/k13_feature_frontend.md).
+
+16-bit PCM wave files (`wav.scp`) are read as well: `read_wav` for one file, `load_wav_scp` for many into one int16 buffer
+for the MFCC kernel (neuralplda_amd/mfcc.py, design/k14_mfcc.md).
 """
 import io
 import os
@@ -19,7 +22,8 @@ import numpy as np
 __all__ = ["read_vector", "read_matrix", "read_plda", "plda_psi_to_pq", "read_vector_ark", "read_vector_scp",
            "read_scp", "load_vector_ark", "load_vector_scp", "write_vector_ark", "fold_init",
            "write_matrix_binary", "write_vector_binary", "write_plda_binary", "read_feature_ark", "read_feature_scp",
-           "load_feature_scp", "FeatureArchive", "FEAT_DESC", "FEAT_FORMATS", "KaldiFormatError"]
+           "load_feature_scp", "FeatureArchive", "FEAT_DESC", "FEAT_FORMATS", "KaldiFormatError", "read_wav",
+           "load_wav_scp", "write_feature_ark"]
 
 
 class KaldiFormatError(ValueError):
@@ -565,6 +569,106 @@ def load_feature_scp(path, entries=None, cols=None):
     return FeatureArchive([k for k, _ in entries], desc, payload)
 
 
+# ---- 16-bit PCM audio (wav.scp) ----------------------------------------------------------------------------------------
+#
+# The audio counterpart of load_feature_scp: every file is memory-mapped, its RIFF chunks are walked, and the chosen
+# channel's int16 samples are copied once into ONE buffer (no float copy on the host: the MFCC kernel reads int16).
+
+_PCM_SUBFORMAT_TAIL = bytes.fromhex("000000001000800000aa00389b71")  # KSDATAFORMAT_SUBTYPE_PCM after its two-byte tag
+
+
+def _wav_layout(buf, off, what):
+    """(sample_rate, channels, byte position of the samples, sample frames) of the RIFF/WAVE object at byte `off` of `buf`:
+    format tag 1, or 0xFFFE (extensible) with the PCM sub-format; 16 bits per sample."""
+    total = len(buf)
+    if off + 12 > total or bytes(buf[off:off + 4]) != b"RIFF" or bytes(buf[off + 8:off + 12]) != b"WAVE":
+        raise KaldiFormatError(f"{what}: not a RIFF/WAVE file")
+    pos, fmt = off + 12, None
+    while pos + 8 <= total:
+        cid = bytes(buf[pos:pos + 4])
+        size = struct.unpack("<I", bytes(buf[pos + 4:pos + 8]))[0]
+        body = pos + 8
+        if cid == b"fmt ":
+            if size < 16 or body + size > total:
+                raise KaldiFormatError(f"{what}: truncated or malformed fmt chunk")
+            tag, ch, rate, _, _, bits = struct.unpack("<HHIIHH", bytes(buf[body:body + 16]))
+            if tag == 0xFFFE:
+                if size < 40:
+                    raise KaldiFormatError(f"{what}: extensible fmt chunk of {size} bytes")
+                sub = bytes(buf[body + 24:body + 40])
+                if sub[2:] != _PCM_SUBFORMAT_TAIL:
+                    raise KaldiFormatError(f"{what}: extensible wave format whose sub-format is not PCM")
+                tag = struct.unpack("<H", sub[:2])[0]
+            if tag != 1:
+                raise KaldiFormatError(f"{what}: wave format tag {tag}, only PCM (1) is read")
+            if bits != 16:
+                raise KaldiFormatError(f"{what}: {bits} bits per sample, only 16-bit PCM is read")
+            if ch < 1:
+                raise KaldiFormatError(f"{what}: {ch} channels")
+            fmt = (rate, ch)
+        elif cid == b"data":
+            if fmt is None:
+                raise KaldiFormatError(f"{what}: data chunk before the fmt chunk")
+            if size == 0 or size == 0xFFFFFFFF:  # a streamed header: to the end of the file
+                size = total - body
+            elif body + size > total:
+                raise KaldiFormatError(f"{what}: truncated data chunk ({size} bytes announced, {total - body} in the file)")
+            return fmt[0], fmt[1], body, size // (2 * fmt[1])
+        pos = body + size + (size & 1)  # chunks are padded to an even size
+    raise KaldiFormatError(f"{what}: no data chunk")
+
+
+def _wav_channel(buf, body, frames, channels, channel, what):
+    if not 0 <= channel < channels:
+        raise KaldiFormatError(f"{what}: channel {channel} of a file with {channels}")
+    return np.frombuffer(buf, dtype="<i2", count=frames * channels, offset=body)[channel::channels]
+
+
+def _is_pipe(rx):
+    return rx.rstrip().endswith("|")
+
+
+def read_wav(f, channel=0):
+    """A wave file (path, or 'path:offset' as an scp names it) -> (sample_rate, int16 array of one channel).  RIFF/WAVE with
+    format tag 1 or the extensible header with the PCM sub-format, 16 bits per sample, any number of channels; other chunks
+    are skipped; a data size of 0 or 0xFFFFFFFF means to the end of the file.  The file is memory-mapped."""
+    f = os.fspath(f)
+    if _is_pipe(f):
+        raise KaldiFormatError(f"{f}: command pipes are not read")
+    path, off = _split_rx(f)
+    buf = np.memmap(path, dtype=np.uint8, mode="r")
+    rate, ch, body, frames = _wav_layout(buf, off or 0, path)
+    return rate, np.array(_wav_channel(buf, body, frames, ch, channel, path), dtype=np.int16)
+
+
+def load_wav_scp(path, entries=None, sample_frequency=None, channel=0):
+    """Kaldi wav.scp -> (keys, offsets int64 (U + 1), samples int16): the chosen channel of every file, one after the other
+    in ONE buffer; utterance u is samples[offsets[u]:offsets[u + 1]].  `entries`: a slice of read_scp(path) to load instead
+    of the whole file.  An entry that is a command pipe (ends in `|`), a file that is not 16-bit PCM, a truncated data
+    chunk, or (if given) a sample rate other than sample_frequency is a KaldiFormatError naming the key.  `segments` files
+    are not read."""
+    if entries is None:
+        entries = read_scp(path)
+    layout, offsets = [], np.zeros(len(entries) + 1, dtype=np.int64)
+    for i, (key, rx) in enumerate(entries):
+        if _is_pipe(rx):
+            raise KaldiFormatError(f"{key}: command pipes in a wav.scp are not read ({rx.strip()!r})")
+        f, off = _split_rx(rx)
+        try:
+            buf = np.memmap(_scp_file(f, path), dtype=np.uint8, mode="r")
+        except (OSError, ValueError) as e:
+            raise KaldiFormatError(f"{key}: cannot map {f}: {e}") from None
+        rate, ch, body, frames = _wav_layout(buf, off or 0, key)
+        if sample_frequency is not None and rate != int(sample_frequency):
+            raise KaldiFormatError(f"{key}: sample rate {rate}, expected {int(sample_frequency)} (there is no resampling)")
+        layout.append(_wav_channel(buf, body, frames, ch, channel, key))
+        offsets[i + 1] = offsets[i] + frames
+    samples = np.empty(int(offsets[-1]), dtype=np.int16)
+    for i, src in enumerate(layout):
+        samples[offsets[i]:offsets[i + 1]] = src
+    return [k for k, _ in entries], offsets, samples
+
+
 # ---- Kaldi initialisation of the model classes --------------------------------------------------------------------
 
 def fold_init(model, mean_vec_file, transform_mat_file, plda_file=None):
@@ -617,6 +721,28 @@ def write_vector_binary(path, v, double=False):
 def write_matrix_binary(path, m, double=False):
     with open(path, "wb") as fh:
         fh.write(b"\0B" + _bin_mat(m, double))
+
+
+def write_feature_ark(ark_path, keys, mats, scp_path=None):
+    """Binary float-matrix archive 'key \\0BFM ...' per matrix (what copy-feats writes uncompressed), optionally with the
+    matching scp.  -> the offsets of the \\0B markers."""
+    if len(keys) != len(mats):
+        raise ValueError("one key per matrix")
+    offsets, pos = [], 0
+    with open(ark_path, "wb") as fh:
+        for k, m in zip(keys, mats):
+            kb = k.encode("ascii") + b" "
+            m = np.asarray(m, dtype=np.float32)
+            if m.ndim != 2:
+                raise ValueError(f"{k}: expected a (frames, columns) matrix")
+            obj = kb + b"\0B" + _bin_mat(m, False)
+            offsets.append(pos + len(kb))
+            fh.write(obj)
+            pos += len(obj)
+    if scp_path is not None:
+        with open(scp_path, "w") as fh:
+            fh.write("".join(f"{k} {ark_path}:{o}\n" for k, o in zip(keys, offsets)))
+    return offsets
 
 
 def write_plda_binary(path, mean, transform, psi):

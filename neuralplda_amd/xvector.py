@@ -344,6 +344,45 @@ class XVectorNet_ETDNN_12Layer(nn.Module):
             return keys, torch.empty((0, XVEC_DIM), dtype=torch.float32, device=dev), dropped
         return keys, (parts[0] if len(parts) == 1 else torch.cat(parts)), dropped
 
+    def extract_from_wav_scp(self, wav_scp, mfcc=None, vad=features.VadOptions(), cmn_window=300, min_frames=25,
+                             utts_per_call=256, device=None, channel=0):
+        """The whole front of the recipe over a Kaldi wav.scp of 16-bit PCM files: `compute-mfcc-feats --dither=0 |
+        compute-vad-energy | apply-cmvn-sliding | select-voiced-frames | nnet3-xvector-compute`, nothing leaving the
+        device in between -> (keys, (len(keys), 512) x-vectors on the device, dropped), as extract_from_scp.  mfcc: an
+        mfcc.MfccOptions with num_ceps == 30 (default: 16 kHz, 30 mel bins, 30 cepstra, 20 - 7600 Hz, snip_edges=false).
+        vad: features.VadOptions, a {key: 0/1 vector} dict, or None.  The scp is worked through utts_per_call lines at a
+        time; the pieces do not change the result (bit for bit).  Inference only."""
+        from . import mfcc as _mfcc
+        if mfcc is None:
+            mfcc = _mfcc.MfccOptions(sample_frequency=16000, num_mel_bins=30, num_ceps=30, low_freq=20, high_freq=7600,
+                                     snip_edges=False)
+        if mfcc.num_ceps != FEAT:
+            raise ValueError(f"MfccOptions.num_ceps = {mfcc.num_ceps}, the extractor takes {FEAT}")
+        if int(min_frames) < CONTEXT + 2:
+            raise ValueError(f"min_frames = {min_frames}: the extractor needs {CONTEXT + 2} frames at least")
+        if int(utts_per_call) < 1:
+            raise ValueError("utts_per_call must be positive")
+        if isinstance(vad, (str, os.PathLike)):
+            raise ValueError("extract_from_wav_scp: vad is VadOptions, a dict of decisions or None (a vad.scp belongs to "
+                             "the feats.scp it was computed from)")
+        dev = _compute_device(self.lin11.weight) if device is None else torch.device(device)
+        entries = kaldi_format.read_scp(wav_scp)
+        keys, dropped, parts = [], [], []
+        for lo in range(0, len(entries), int(utts_per_call)):
+            piece = entries[lo:lo + int(utts_per_call)]
+            pkeys, offsets, samples = kaldi_format.load_wav_scp(wav_scp, entries=piece,
+                                                                sample_frequency=mfcc.sample_frequency, channel=channel)
+            frames, lengths = _mfcc.compute_mfcc(samples, offsets, mfcc, dev)
+            prep = features.prepare_frames(pkeys, frames, lengths, vad, cmn_window, min_frames)
+            keys += prep.keys
+            dropped += prep.dropped
+            if prep.keys:
+                with torch.no_grad():
+                    parts.append(self.extract_ragged(prep.frames, prep.lengths))
+        if not parts:
+            return keys, torch.empty((0, XVEC_DIM), dtype=torch.float32, device=dev), dropped
+        return keys, (parts[0] if len(parts) == 1 else torch.cat(parts)), dropped
+
     # -- Kaldi -----------------------------------------------------------------------------------
     def LoadFromKaldi(self, weightspath):
         """utils/models.py:188-214: a pickle of {component: {'params' | 'bias' | 'stats-mean' | 'stats-var': ndarray}}."""

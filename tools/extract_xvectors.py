@@ -4,12 +4,16 @@
     python tools/extract_xvectors.py data/test/feats.scp --vad-scp data/test/vad.scp --model model.pt \\
         --out-ark xvector.ark --out-scp xvector.scp
     python tools/extract_xvectors.py data/test/feats.scp --vad-conf conf/vad.conf --model etdnn_weights.pkl ...
+    python tools/extract_xvectors.py --wav-scp data/test/wav.scp --mfcc-config conf/mfcc.conf --model model.pt ...
 
 feats.scp may point at FM, DM, CM, CM2 or CM3 matrices (make_mfcc.sh writes CM).  The frames are decoded, normalised
 (sliding mean, --cmn-window) and selected (--vad-scp: given decisions; --vad-conf: energy VAD with that file's options;
 neither: energy VAD with the recipe's defaults; --no-vad: every frame) on the device, and the x-vectors are written as a
 binary vector archive that kaldi_format.load_vector_scp and the score generators read.  Utterances with fewer than
 --min-frames voiced frames are listed on stderr and left out.
+
+--wav-scp (instead of feats.scp): 16-bit PCM wave files; their MFCCs are computed on the device first (compute-mfcc-feats
+with --dither=0 and the options of --mfcc-config, which must give 30 cepstra; default 16 kHz, 30 bins, 20 - 7600 Hz).
 
 --model: a pickled / torch.save'd XVectorNet_ETDNN_12Layer or Etdnn_Xvec_NeuralPlda, a state dict of either, or the
 recipe's pickle of Kaldi weights ({'tdnn1.affine': {'params': ...}, ...}, what LoadFromKaldi reads)."""
@@ -55,7 +59,10 @@ def load_extractor(path, pooling, dev):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("feats_scp")
+    ap.add_argument("feats_scp", nargs="?", default=None)
+    ap.add_argument("--feats-scp", dest="feats_scp_opt", default=None, help="the same as the positional argument")
+    ap.add_argument("--wav-scp", default=None, help="16-bit PCM wave files instead of features")
+    ap.add_argument("--mfcc-config", default=None, help="a Kaldi mfcc.conf for --wav-scp")
     g = ap.add_mutually_exclusive_group()
     g.add_argument("--vad-scp", help="given 0/1 decisions per frame (compute-vad-energy's output)")
     g.add_argument("--vad-conf", help="energy VAD on the device with the --vad-* options of this file")
@@ -69,6 +76,13 @@ def main(argv=None):
     ap.add_argument("--utts-per-call", type=int, default=2048)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
+    feats_scp = a.feats_scp or a.feats_scp_opt
+    if (feats_scp is None) == (a.wav_scp is None) or (a.feats_scp and a.feats_scp_opt):
+        ap.error("give one of feats.scp (positional or --feats-scp) and --wav-scp")
+    if a.wav_scp is None and a.mfcc_config:
+        ap.error("--mfcc-config goes with --wav-scp")
+    if a.wav_scp is not None and a.vad_scp:
+        ap.error("--vad-scp goes with a feats.scp (its decisions belong to those frames)")
     from neuralplda_amd import features, kaldi_format
     dev = torch.device(a.device)
     m = load_extractor(a.model, a.pooling, dev)
@@ -78,8 +92,14 @@ def main(argv=None):
         vad = a.vad_scp
     else:
         vad = features.VadOptions.from_conf(a.vad_conf) if a.vad_conf else features.VadOptions()
-    keys, xv, dropped = m.extract_from_scp(a.feats_scp, vad=vad, cmn_window=a.cmn_window, min_frames=a.min_frames,
-                                           utts_per_call=a.utts_per_call, device=dev)
+    if a.wav_scp is not None:
+        from neuralplda_amd import mfcc
+        keys, xv, dropped = m.extract_from_wav_scp(a.wav_scp, mfcc=mfcc.MfccOptions.from_conf(a.mfcc_config) if a.mfcc_config
+                                                   else None, vad=vad, cmn_window=a.cmn_window, min_frames=a.min_frames,
+                                                   utts_per_call=min(a.utts_per_call, 256), device=dev)
+    else:
+        keys, xv, dropped = m.extract_from_scp(feats_scp, vad=vad, cmn_window=a.cmn_window, min_frames=a.min_frames,
+                                               utts_per_call=a.utts_per_call, device=dev)
     kaldi_format.write_vector_ark(a.out_ark, keys, xv.cpu().numpy(), a.out_scp)
     for k, n in dropped:
         print(f"dropped {k}: {n} voiced frames (fewer than {a.min_frames})", file=sys.stderr)
