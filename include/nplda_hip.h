@@ -755,6 +755,27 @@ int nplda_mfcc_frames_f32(const int16_t* samples, const int64_t* sample_offsets,
                           int64_t total_frames, const nplda_mfcc_geometry* geometry, const float* window, const void* dft_image,
                           const void* bank_image, const void* dct_image, float* out, nplda_stream_t stream);
 
+/* ---- class scatter of x-vector rows (LDA / PLDA estimation, neuralplda_amd/backend.py) ------------------------ */
+
+/* With x_k = table[rows[k]][0:n] - pivot (rows == NULL: row k itself; pivot == NULL: 0) for the N positions k, of which
+ * offs[s] .. offs[s + 1] belong to class s (offs: S + 1 DEVICE int64, non-decreasing, offs[0] = 0, offs[S] = N):
+ *     sum[i] = sum_k x_k[i],   scatter[i][j] = sum_k x_k[i] x_k[j],   class_sum[s][i] = sum_{k in s} x_k[i]
+ * — what ivector-mean, ivector-compute-lda and ivector-compute-plda accumulate.  Outputs are DEVICE doubles: sum (n),
+ * scatter (n, n), class_sum (S, n).  accumulate != 0 adds into sum and scatter (training sets can be streamed); class_sum is
+ * always overwritten, an empty class gives a zero row.  Products are exact fp32 on MFMA, summed in fp32 over row groups of
+ * 1024 and in fp64, in a fixed order, across them: no atomics, the same bits on every call, scatter exactly symmetric.  The
+ * pivot is subtracted BEFORE the product: pass an estimate of the mean, so that data far from the origin does not cancel in
+ * fp32.  Row indices are clamped into [0, table_rows) as in nplda_embed_rows_f32 (callers validate them).
+ * Requires n % 4 == 0, n <= 512 (else NPLDA_EUNSUPPORTED), ldt % 4 == 0, ldt >= n, table / pivot / ws 16-byte aligned
+ * (else NPLDA_EINVAL); nothing is launched then.  N == 0: zeros (sum and scatter untouched under accumulate).
+ * ws: nplda_class_scatter_workspace_bytes(N, S, n) bytes (0 for an unsupported n).  The environment variable
+ * NPLDA_SCATTER_MAX_CHUNKS (read by both functions at every call) lowers the number of fp64 slabs the GEMM keeps: less
+ * workspace, the same result to the last bit. */
+size_t nplda_class_scatter_workspace_bytes(int64_t N, int64_t S, int n);
+int nplda_class_scatter_f32(const float* table, int64_t table_rows, int64_t ldt, const int64_t* rows, int64_t N,
+                            const int64_t* offs, int64_t S, int n, const float* pivot, double* sum, double* scatter,
+                            double* class_sum, int accumulate, void* ws, size_t ws_bytes, nplda_stream_t stream);
+
 /* ---- measurement utility ------------------------------------------------------------------------------------- */
 
 /* Shader-clock probe for bench.py (no reference counterpart): one wave that stays resident for window_us microseconds

@@ -201,6 +201,9 @@ SIGNATURES = {
     "nplda_mfcc_image_bytes": (_c_sz, [_c_vp, _c_int]),
     "nplda_mfcc_frames_f32": (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_f32p, _c_vp, _c_vp, _c_vp, _c_f32p,
                                        _c_vp]),
+    "nplda_class_scatter_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_int]),
+    "nplda_class_scatter_f32": (_c_int, [_c_f32p, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp, _c_i64, _c_int, _c_f32p, _c_vp, _c_vp,
+                                         _c_vp, _c_int, _c_vp, _c_sz, _c_vp]),
     "gb_score_pairs_ex_f32": (_c_int, [_c_f32p, _c_f32p, _c_i64, _c_i64, _c_vp, _c_int, _c_int, _c_f32p, _c_f32p,
                                        _c_f32p, _c_vp]),
 }

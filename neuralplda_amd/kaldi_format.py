@@ -12,6 +12,10 @@ many into one buffer for the device decoder (neuralplda_amd/features.py, design/
 
 16-bit PCM wave files (`wav.scp`) are read as well: `read_wav` for one file, `load_wav_scp` for many into one int16 buffer
 for the MFCC kernel (neuralplda_amd/mfcc.py, design/k14_mfcc.md).
+
+The objects themselves no longer have to come from Kaldi: neuralplda_amd/backend.py estimates `mean.vec`, `transform.mat`
+and `plda` from x-vectors on the GPU, writes them with the writers below, and folds its arrays into a model through
+`fold_arrays`, the array-level half of `fold_init` (design/k15_backend_estimation.md).
 """
 import io
 import os
@@ -23,7 +27,7 @@ __all__ = ["read_vector", "read_matrix", "read_plda", "plda_psi_to_pq", "read_ve
            "read_scp", "load_vector_ark", "load_vector_scp", "write_vector_ark", "fold_init",
            "write_matrix_binary", "write_vector_binary", "write_plda_binary", "read_feature_ark", "read_feature_scp",
            "load_feature_scp", "FeatureArchive", "FEAT_DESC", "FEAT_FORMATS", "KaldiFormatError", "read_wav",
-           "load_wav_scp", "write_feature_ark"]
+           "load_wav_scp", "write_feature_ark", "fold_arrays"]
 
 
 class KaldiFormatError(ValueError):
@@ -680,15 +684,25 @@ def fold_init(model, mean_vec_file, transform_mat_file, plda_file=None):
       P_sqrt, Q                    <- sqrt(diagP), diagQ of plda_psi_to_pq(Psi)
     The parameters are written through `.data` like the reference does and their version counters are bumped, so cached
     parameter images are rebuilt."""
-    import torch
-    T = read_matrix(transform_mat_file)
-    mean = read_vector(mean_vec_file)
-    new = {"centering_and_LDA.weight": T[:, :-1], "centering_and_LDA.bias": T[:, -1] - T[:, :-1].dot(mean)}
+    plda = None
     if plda_file is not None:
-        plda = read_plda(plda_file)
-        D = plda["diagonalizing_transform"]
-        new.update({"centering_and_wccn_plda.weight": D, "centering_and_wccn_plda.bias": -D.dot(plda["plda_mean"]),
-                    "P_sqrt": np.sqrt(plda["diagP"]), "Q": plda["diagQ"]})
+        d = read_plda(plda_file)
+        plda = (d["plda_mean"], d["diagonalizing_transform"], d["Psi_across_covar_diag"])
+    fold_arrays(model, read_vector(mean_vec_file), read_matrix(transform_mat_file), plda)
+
+
+def fold_arrays(model, mean_vec, transform_mat, plda=None):
+    """The array-level half of fold_init: mean_vec (D0), transform_mat (D1, D0 + 1) and optionally plda = (plda_mean,
+    diagonalizing transform, Psi) as arrays — what the files hold, or what neuralplda_amd.backend estimated."""
+    import torch
+    T = np.asarray(transform_mat, dtype=np.float64)
+    mean = np.asarray(mean_vec, dtype=np.float64)
+    new = {"centering_and_LDA.weight": T[:, :-1], "centering_and_LDA.bias": T[:, -1] - T[:, :-1].dot(mean)}
+    if plda is not None:
+        plda_mean, D, psi = (np.asarray(a, dtype=np.float64) for a in plda)
+        diagP, diagQ = plda_psi_to_pq(psi)
+        new.update({"centering_and_wccn_plda.weight": D, "centering_and_wccn_plda.bias": -D.dot(plda_mean),
+                    "P_sqrt": np.sqrt(diagP), "Q": diagQ})
     sd = model.state_dict()
     for name, val in new.items():
         sd[name].data.copy_(torch.from_numpy(np.ascontiguousarray(val)).float())

@@ -355,6 +355,21 @@ class _LossFn(torch.autograd.Function):
 # NeuralPlda
 # ---------------------------------------------------------------------------------------------------
 
+def _fit_device(model):
+    """The device an estimate for `model` runs on: the model's own when it lives on a HIP device, else the current one."""
+    dev = model.centering_and_LDA.weight.device
+    return dev if dev.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
+
+
+def _init_lda_from_xvectors(model, table, spk2utt, kw):
+    from . import backend
+    kw.setdefault("lda_dim", model.centering_and_LDA.out_features)
+    kw.setdefault("device", _fit_device(model))
+    be = backend.fit_backend(table, spk2utt, plda=False, **kw)
+    be.apply(model)
+    return be
+
+
 class NeuralPlda(nn.Module):
     """Drop-in for utils/models.py:348-461.  `nc` is any object with the NpldaConf fields the reference
     constructor reads (xvector_dim, layer1_LDA_dim, layer2_PLDA_spkfactor_dim, beta, alpha, device, loss)."""
@@ -514,6 +529,18 @@ class NeuralPlda(nn.Module):
         """utils/models.py:441-457, reading the Kaldi files natively (no Kaldi binaries needed)."""
         kaldi_format.fold_init(self, mean_vec_file, transform_mat_file, PldaFile)
 
+    def InitFromXvectors(self, table, spk2utt, **kw):
+        """The initialisation LoadPldaParamsFromKaldi reads from Kaldi's files, estimated here from an XvectorTable and a
+        spk2utt (neuralplda_amd.backend.fit_backend; lda_dim / plda_dim default to this model's layer sizes) -> the Backend,
+        whose save() writes those files."""
+        from . import backend
+        kw.setdefault("lda_dim", self.centering_and_LDA.out_features)
+        kw.setdefault("plda_dim", self.centering_and_wccn_plda.out_features)
+        kw.setdefault("device", _fit_device(self))
+        be = backend.fit_backend(table, spk2utt, **kw)
+        be.apply(self)
+        return be
+
     def SaveModel(self, filename):
         """utils/models.py:459-461: pickle of the whole module."""
         with open(filename, 'wb') as f:
@@ -599,6 +626,10 @@ class DPlda(NeuralPlda):
     def LoadParamsFromKaldi(self, mean_vec_file, transform_mat_file):
         """utils/models.py:551-564."""
         kaldi_format.fold_init(self, mean_vec_file, transform_mat_file)
+
+    def InitFromXvectors(self, table, spk2utt, **kw):
+        """LoadParamsFromKaldi without Kaldi: mean.vec and the LDA estimated from x-vectors (backend.fit_backend, LDA only)."""
+        return _init_lda_from_xvectors(self, table, spk2utt, kw)
 
     def LoadPldaParamsFromKaldi(self, *a, **k):
         raise AttributeError("DPlda has no PLDA layer; use LoadParamsFromKaldi(mean_vec_file, transform_mat_file)")
@@ -701,6 +732,10 @@ class GaussianBackend(nn.Module):
     def LoadPldaParamsFromKaldi(self, mean_vec_file, transform_mat_file):
         """utils/models.py:653-658."""
         kaldi_format.fold_init(self, mean_vec_file, transform_mat_file)
+
+    def InitFromXvectors(self, table, spk2utt, **kw):
+        """LoadPldaParamsFromKaldi without Kaldi: mean.vec and the LDA estimated from x-vectors (backend.fit_backend, LDA only)."""
+        return _init_lda_from_xvectors(self, table, spk2utt, kw)
 
     def SaveModel(self, filename):
         with open(filename, 'wb') as f:

@@ -1413,6 +1413,76 @@ def weighted_moments(x, w0, w1=None, out=None):
     return cnt, sm, sq
 
 
+def class_scatter(table, offs, rows=None, pivot=None, n=None, out=None, validate=True):
+    """nplda_class_scatter_f32: with x_k = table[rows[k]][:n] - pivot (rows None: the first offs[-1] rows in order; pivot None:
+    0; n None: every column) -> (sum (n,), scatter (n, n), class_sum (S, n)) device doubles, class s = positions
+    offs[s] .. offs[s + 1] (offs: S + 1 int64, non-decreasing from 0).  `out` = the (sum, scatter) of a previous call to add
+    into (streamed training sets; class_sum is this call's alone).  `validate` checks offs and the row indices (one
+    device-to-host sync); the kernel itself only clamps."""
+    lib = _lib.load()
+    _require_dev_f32(table, "table")
+    if table.dim() != 2:
+        raise ValueError("table must be 2-D")
+    dev = table.device
+    n = table.shape[1] if n is None else int(n)
+    if n <= 0 or n > table.shape[1]:
+        raise ValueError(f"n must be in 1 .. {table.shape[1]}")
+    if n % 4 != 0:
+        raise ValueError(f"row length must be a multiple of 4 (got {n})")
+    if table.stride(1) != 1 or table.stride(0) % 4 != 0 or table.stride(0) < n or table.data_ptr() % 16 != 0:
+        table = table.contiguous()
+    ldt = table.stride(0) if table.shape[0] > 1 else max(table.shape[1], 4)
+    if not isinstance(offs, torch.Tensor) or offs.dtype != torch.int64 or offs.dim() != 1 or offs.numel() < 1:
+        raise ValueError("offs must be a 1-D int64 tensor of S + 1 offsets")
+    offs = offs.to(dev).contiguous()
+    S = offs.numel() - 1
+    if rows is not None:
+        if rows.dtype != torch.int64 or rows.dim() != 1:
+            raise ValueError("rows must be a 1-D int64 tensor")
+        rows = rows.to(dev).contiguous()
+    if validate:
+        o = offs.cpu()
+        N = int(o[-1])
+        if int(o[0]) != 0 or bool((o[1:] < o[:-1]).any()):
+            raise ValueError("offs must start at 0 and not decrease")
+        if rows is not None and N > 0 and (rows.numel() != N or int(rows.min()) < 0 or int(rows.max()) >= table.shape[0]):
+            raise ValueError("rows must hold offs[-1] indices into the table")
+    else:
+        N = rows.numel() if rows is not None else int(offs[-1])
+    if rows is None and N > table.shape[0]:
+        raise ValueError("offs[-1] exceeds the number of table rows")
+    if S == 0 and N != 0:
+        raise ValueError("rows without a class")
+    if pivot is not None:
+        _require_dev_f32(pivot, "pivot")
+        if pivot.numel() != n:
+            raise ValueError(f"pivot must have {n} entries")
+        pivot = pivot.contiguous()
+        if pivot.data_ptr() % 16 != 0:  # pragma: no cover (torch allocations are >= 256-B aligned; a view may not be)
+            pivot = pivot.clone()
+    if out is None:
+        sm = torch.empty(n, dtype=torch.float64, device=dev)
+        sc = torch.empty((n, n), dtype=torch.float64, device=dev)
+        acc = 0
+    else:
+        sm, sc = out
+        if sm.shape != (n,) or sc.shape != (n, n) or sm.dtype != torch.float64 or sc.dtype != torch.float64 or \
+                not sm.is_contiguous() or not sc.is_contiguous():
+            raise ValueError("`out` does not match this call")
+        acc = 1
+    cs = torch.empty((S, n), dtype=torch.float64, device=dev)
+    nbytes = lib.nplda_class_scatter_workspace_bytes(N, S, n)
+    if nbytes == 0:
+        raise _lib.NpldaHipError(f"row length {n} is outside the compiled kernel set (n % 4 == 0, n <= 512)")
+    wsb = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    with _lib.on_device(dev):
+        code = lib.nplda_class_scatter_f32(_lib.ptr(table), table.shape[0], ldt, _lib.ptr(rows), N, _lib.ptr(offs), S, n,
+                                           _lib.ptr(pivot), _lib.ptr(sm), _lib.ptr(sc), _lib.ptr(cs), acc, _lib.ptr(wsb), nbytes,
+                                           _lib.current_stream())
+    _lib.check(code, "nplda_class_scatter_f32")
+    return sm, sc, cs
+
+
 def dplda_fold_grad(cnt, sm, sq, D1, reduce=None):
     """(cnt, sum, sq) of paired rows weighted by g = dL/ds -> gradient of DPlda's linear unit (utils/models.py:484-490):
     d wlr = [G12 + G21 | G11 + G22 | s1 + s2] (row-major blocks of G = sum g x x^T), d bias = sum g.
