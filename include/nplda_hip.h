@@ -438,6 +438,82 @@ int nplda_detcost_sweep_f32(const float* scores, const float* target, int64_t N,
                             float* minc, float* thr, float* minc_avg, float* eer, void* workspace,
                             size_t workspace_bytes, nplda_stream_t stream);
 
+/* ---- score calibration and fusion (csrc/nplda_calib.hip; counterpart of utils/score_calibration.py) ---------------- */
+
+/* Notation: X (N, K) scores of K <= 8 systems, fp32 (_f32) or fp64 (_f64), row stride ldx >= K elements; target (N)
+ * fp32, target iff t > 0.5, non-target iff t < 0.5, neither: the trial is ignored; theta = (a_1 .. a_K, b), K + 1 DEVICE
+ * doubles; tau = logit(p_target); z_i = sum_k a_k X_ik + b + tau; w_i = p_target / N_tgt on targets and
+ * (1 - p_target) / N_non on non-targets.  All arithmetic is fp64; every sum over trials is a fixed-order tree (no
+ * floating-point atomics: the same input gives the same bits) and a plain sum over trials.
+ * Every entry point checks its arguments before anything is enqueued: K outside 1 .. 8 or N >= 2^31 ->
+ * NPLDA_EUNSUPPORTED; a null pointer, N < 2 (fits, pass) / N < 1 (costs) / N < 0 (apply), ldx < K, p_target outside
+ * (0, 1), l2 < 0, a workspace that is null or not 16-byte aligned -> NPLDA_EINVAL; a workspace smaller than
+ * nplda_calib_workspace_bytes(N, K) -> NPLDA_ENOSPC.  nplda_calib_workspace_bytes returns 0 for an unsupported size
+ * (N < 2, N >= 2^31, K outside 1 .. 8); it does not decrease with N.  gauss_fit and costs take the workspace of K = 1. */
+size_t nplda_calib_workspace_bytes(int64_t N, int K);
+/* Rows one full sweep of the reduction grid covers (blocks x threads): above it a lane sums more than one trial. */
+int nplda_calib_sweep_rows(void);
+
+/* One pass of the prior-weighted logistic objective at theta.  out (DEVICE doubles, 2 + 1 + (K + 1) + (K + 1)(K + 2) / 2):
+ *   N_tgt, N_non,
+ *   J = sum_i w_i softplus(-z_i | target, +z_i | non-target) + (l2 / 2) sum_k a_k^2,
+ *   g = sum_i w_i (sigma(z_i) - t_i) [X_i, 1] + l2 [a, 0]                                   (K + 1),
+ *   H = sum_i w_i sigma_i (1 - sigma_i) [X_i, 1][X_i, 1]^T + l2 diag(1 .. 1, 0), upper triangle by rows.
+ * softplus and sigma are evaluated in their overflow-safe forms. */
+int nplda_calib_logreg_pass_f32(const float* X, int64_t N, int64_t ldx, int K, const float* target, const double* theta,
+                                double p_target, double l2, double* out, void* workspace, size_t workspace_bytes,
+                                nplda_stream_t stream);
+int nplda_calib_logreg_pass_f64(const double* X, int64_t N, int64_t ldx, int K, const float* target, const double* theta,
+                                double p_target, double l2, double* out, void* workspace, size_t workspace_bytes,
+                                nplda_stream_t stream);
+
+/* Damped Newton fit: enqueues a FIXED budget of max_passes (1 .. 256) pairs of launches (pass | finish + step) on the
+ * stream with no host synchronisation; the step solves H d = g by Cholesky, accepts theta - alpha d if J did not
+ * increase (beyond 8 ulp of J, the rounding of the sum) and halves alpha otherwise, at most 20 times in a row.  Once a
+ * stop flag is set the remaining launches return at once.  theta (in: the start, out: ALWAYS the last accepted value).
+ * resume = 0 starts a fit; resume = 1 continues the fit whose state is in `workspace` with another budget (so that a
+ * caller can enqueue the budget in pieces and look at the flags in between).  report (10 DEVICE doubles): J and
+ * max |g_k| at theta, iterations (accepted Newton directions), passes, converged (max |g_k| <= tol), not_finite (J, g or H
+ * not finite, an empty class, or the Cholesky failed), stalled (20 halvings did not lower J), N_tgt, N_non, last alpha. */
+int nplda_calib_logreg_fit_f32(const float* X, int64_t N, int64_t ldx, int K, const float* target, double* theta,
+                               double p_target, double l2, int max_passes, double tol, int resume, double* report,
+                               void* workspace, size_t workspace_bytes, nplda_stream_t stream);
+int nplda_calib_logreg_fit_f64(const double* X, int64_t N, int64_t ldx, int K, const float* target, double* theta,
+                               double p_target, double l2, int max_passes, double tol, int resume, double* report,
+                               void* workspace, size_t workspace_bytes, nplda_stream_t stream);
+
+/* One Gaussian per class (utils/score_calibration.py:14-24).  out (6 DEVICE doubles): count, mean and POPULATION
+ * standard deviation (ddof = 0, np.std) of the targets, then of the non-targets; two passes (sums, then squared
+ * deviations about the means), an empty class gives NaN. */
+int nplda_calib_gauss_fit_f32(const float* scores, const float* target, int64_t N, double* out, void* workspace,
+                              size_t workspace_bytes, nplda_stream_t stream);
+int nplda_calib_gauss_fit_f64(const double* scores, const float* target, int64_t N, double* out, void* workspace,
+                              size_t workspace_bytes, nplda_stream_t stream);
+
+/* out_i = sum_k a_k X_ik + b (one fma chain from b); out: N floats (out_f64 = 0) or doubles (out_f64 = 1). */
+int nplda_calib_apply_linear_f32(const float* X, int64_t N, int64_t ldx, int K, const double* theta, void* out,
+                                 int out_f64, nplda_stream_t stream);
+int nplda_calib_apply_linear_f64(const double* X, int64_t N, int64_t ldx, int K, const double* theta, void* out,
+                                 int out_f64, nplda_stream_t stream);
+
+/* out_i = log std_imp - log std_tgt - (s - mu_tgt)^2 / (2 std_tgt^2) + (s - mu_imp)^2 / (2 std_imp^2), in this form
+ * (utils/score_calibration.py:26-28: the difference of two normal log densities).  Standard deviations that are not
+ * positive and finite, or a mean that is not finite -> NPLDA_EINVAL. */
+int nplda_calib_apply_gauss_f32(const float* scores, int64_t N, double mu_tgt, double std_tgt, double mu_imp,
+                                double std_imp, void* out, int out_f64, nplda_stream_t stream);
+int nplda_calib_apply_gauss_f64(const double* scores, int64_t N, double mu_tgt, double std_tgt, double mu_imp,
+                                double std_imp, void* out, int out_f64, nplda_stream_t stream);
+
+/* Calibration-sensitive costs of N log-likelihood ratios at nth <= 8 thresholds (HOST doubles, +-inf allowed, NaN ->
+ * NPLDA_EINVAL).  counts (2 + 2 nth DEVICE int64): N_tgt, N_non, misses (llr < th on a target) per threshold, false
+ * alarms (llr >= th on a non-target) per threshold — the decision rule of nplda_detcost_sweep_f32's exact mode.
+ * sums (2 DEVICE doubles): sum_tgt log2(1 + exp(-llr)), sum_non log2(1 + exp(llr)) — Cllr = (sums[0] / N_tgt +
+ * sums[1] / N_non) / 2. */
+int nplda_calib_costs_f32(const float* llr, const float* target, int64_t N, const double* thresholds, int nth,
+                          int64_t* counts, double* sums, void* workspace, size_t workspace_bytes, nplda_stream_t stream);
+int nplda_calib_costs_f64(const double* llr, const float* target, int64_t N, const double* thresholds, int nth,
+                          int64_t* counts, double* sums, void* workspace, size_t workspace_bytes, nplda_stream_t stream);
+
 /* ---- host-side text I/O of the trial-list path (no device work; plain host pointers) ------------------------------ */
 
 /* Rows and columns of a whitespace-separated table held in memory, with np.genfromtxt(dtype=str) semantics (the

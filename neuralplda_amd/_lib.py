@@ -77,6 +77,20 @@ SIGNATURES = {
     "nplda_detcost_workspace_bytes": (_c_sz, [_c_i64]),
     "nplda_detcost_sweep_f32": (_c_int, [_c_f32p, _c_f32p, _c_i64, ctypes.POINTER(ctypes.c_float), _c_int, _c_int, _c_f32p,
                                          _c_f32p, _c_f32p, _c_f32p, _c_vp, _c_sz, _c_vp]),
+    "nplda_calib_workspace_bytes": (_c_sz, [_c_i64, _c_int]),
+    "nplda_calib_sweep_rows": (_c_int, []),
+    **{f"nplda_calib_logreg_pass_{p}": (_c_int, [_c_vp, _c_i64, _c_i64, _c_int, _c_f32p, _c_vp, ctypes.c_double,
+                                                 ctypes.c_double, _c_vp, _c_vp, _c_sz, _c_vp]) for p in ("f32", "f64")},
+    **{f"nplda_calib_logreg_fit_{p}": (_c_int, [_c_vp, _c_i64, _c_i64, _c_int, _c_f32p, _c_vp, ctypes.c_double,
+                                                ctypes.c_double, _c_int, ctypes.c_double, _c_int, _c_vp, _c_vp, _c_sz,
+                                                _c_vp]) for p in ("f32", "f64")},
+    **{f"nplda_calib_gauss_fit_{p}": (_c_int, [_c_vp, _c_f32p, _c_i64, _c_vp, _c_vp, _c_sz, _c_vp]) for p in ("f32", "f64")},
+    **{f"nplda_calib_apply_linear_{p}": (_c_int, [_c_vp, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_vp])
+       for p in ("f32", "f64")},
+    **{f"nplda_calib_apply_gauss_{p}": (_c_int, [_c_vp, _c_i64] + [ctypes.c_double] * 4 + [_c_vp, _c_int, _c_vp])
+       for p in ("f32", "f64")},
+    **{f"nplda_calib_costs_{p}": (_c_int, [_c_vp, _c_f32p, _c_i64, ctypes.POINTER(ctypes.c_double), _c_int, _c_vp, _c_vp,
+                                           _c_vp, _c_sz, _c_vp]) for p in ("f32", "f64")},
     "nplda_text_scan": (_c_i64, [ctypes.c_char_p, _c_sz, ctypes.POINTER(_c_int)]),
     "nplda_text_lookup": (_c_int, [ctypes.c_char_p, _c_sz, _c_i64, _c_int, _c_int, _c_int, ctypes.c_char_p, _c_vp, _c_vp,
                                    _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64)]),

@@ -8,12 +8,22 @@ CPU tensors are moved to the HIP device first — like the rest of the package t
   (utils/models.py:23-27 `arr2val`): the "count" is the last index of torch.where (= count - 1) and
   1.0 when the set is empty; thresholds are swept over the target scores only.
 * reference_semantics=False: the exact minimum of P_miss + beta * P_fa over all thresholds.
+
+Calibration-sensitive metrics (no reference counterpart; kernel nplda_calib_costs_*, csrc/nplda_calib.hip) take
+log-likelihood ratios instead of arbitrary scores:
+
+* cllr(llr, target): the cost of the LLRs as soft decisions, in bits (0 = perfect, 1 = as good as no system).
+* act_cost(llr, target, betas): P_miss + beta * P_fa at the Bayes threshold log(beta) — the cost, beta convention
+  (NpldaConf's `beta`) and normalisation of minc_exact, whose minimum over thresholds it can only exceed.
+* act_dcf(llr, target, p_target, c_miss, c_fa): the same counts in NIST's normalisation.
 """
+import math
+
 import torch
 
 from . import _lib, ops
 
-__all__ = ["minc", "eer", "minc_exact"]
+__all__ = ["minc", "eer", "minc_exact", "cllr", "act_cost", "act_dcf"]
 
 
 def _on_device(output, target):
@@ -54,3 +64,57 @@ def eer(output, target):
     """Equal error rate (linear interpolation at the P_miss / P_fa crossing)."""
     _, _, _, e = _sweep(output, target, [1.0], exact=True, want_eer=True)
     return float(e.item())
+
+
+def _llr_on_device(llr, target):
+    dev = None
+    for t in (llr, target):
+        if isinstance(t, torch.Tensor) and t.is_cuda:
+            dev = t.device
+            break
+    if dev is None:
+        if not torch.cuda.is_available():
+            raise _lib.NpldaHipError("calibration metrics need a HIP device (there is no CPU implementation)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+    s = torch.as_tensor(llr).detach().reshape(-1)
+    if s.dtype not in (torch.float32, torch.float64):
+        s = s.to(torch.float64)
+    t = torch.as_tensor(target).detach().reshape(-1).to(torch.float32)
+    return s.to(dev), t.to(dev)
+
+
+def _rates(llr, target, thresholds):
+    """Host numbers of one nplda_calib_costs_* call: (N_tgt, N_non, misses [..], false alarms [..], Cllr sums (2))."""
+    s, t = _llr_on_device(llr, target)
+    cnt, miss, fa, sums = ops.calib_costs(s, t, thresholds)
+    nt, nn = cnt.tolist()
+    if nt < 1 or nn < 1:
+        raise ValueError(f"the metric needs trials of both classes (got {nt} targets, {nn} non-targets)")
+    return nt, nn, miss.tolist(), fa.tolist(), sums.tolist()
+
+
+def cllr(llr, target):
+    """Cllr = (mean_tgt log2(1 + exp(-llr)) + mean_non log2(1 + exp(llr))) / 2, a float."""
+    nt, nn, _, _, sums = _rates(llr, target, ())
+    return 0.5 * (sums[0] / nt + sums[1] / nn)
+
+
+def act_cost(llr, target, betas):
+    """-> (average over betas, {beta: P_miss + beta * P_fa}) with the decision 'target' iff llr >= log(beta): minc_exact's
+    cost at the threshold a calibrated system would use instead of at the best one."""
+    betas = list(betas)
+    if not betas:
+        raise ValueError("at least one beta")
+    nt, nn, miss, fa, _ = _rates(llr, target, [math.log(b) for b in betas])
+    costs = [miss[k] / nt + b * (fa[k] / nn) for k, b in enumerate(betas)]
+    return sum(costs) / len(costs), dict(zip(betas, costs))  # the average counts a repeated beta as often as it is given
+
+
+def act_dcf(llr, target, p_target, c_miss=1.0, c_fa=1.0):
+    """NIST's normalised actual DCF: (c_miss p_target P_miss + c_fa (1 - p_target) P_fa) / min(c_miss p_target,
+    c_fa (1 - p_target)) at the threshold log(c_fa (1 - p_target) / (c_miss p_target))."""
+    if not 0.0 < p_target < 1.0 or c_miss <= 0.0 or c_fa <= 0.0:
+        raise ValueError("p_target must lie strictly between 0 and 1, the costs must be positive")
+    wm, wf = c_miss * p_target, c_fa * (1.0 - p_target)
+    nt, nn, miss, fa, _ = _rates(llr, target, [math.log(wf / wm)])
+    return (wm * miss[0] / nt + wf * fa[0] / nn) / min(wm, wf)

@@ -1521,3 +1521,186 @@ def detcost_sweep(scores, target, betas, exact=False, want_eer=False):
                                            _lib.current_stream())
     _lib.check(code, "nplda_detcost_sweep_f32")
     return out[:K], out[K:2 * K], out[2 * K:2 * K + 1], (out[2 * K + 1:] if want_eer else None)
+
+
+def _require_dev_float(t, name):
+    """_require_dev_f32's twin for the calibration entry points, which take fp32 or fp64 scores."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not t.is_cuda:
+        raise _lib.NpldaHipError(f"{name} must live on a HIP device (got {t.device}); there is no CPU path")
+    if t.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{name} must be float32 or float64 (got {t.dtype})")
+    return "f32" if t.dtype == torch.float32 else "f64"
+
+
+def _require_dev_f64(t, name, numel=None, device=None):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not t.is_cuda:
+        raise _lib.NpldaHipError(f"{name} must live on a HIP device (got {t.device}); there is no CPU path")
+    if t.dtype != torch.float64:
+        raise TypeError(f"{name} must be float64 (got {t.dtype})")
+    if numel is not None and t.numel() != numel:
+        raise ValueError(f"{name} must have {numel} entries (got {t.numel()})")
+    if device is not None and t.device != device:
+        raise ValueError(f"{name} must live on the device of the scores ({device}, got {t.device})")
+
+
+def _calib_scores(X, name="scores"):
+    """(tensor with unit inner stride, N, K, ldx, type suffix): (N,) is one system; a row-strided view is used as it is."""
+    sfx = _require_dev_float(X, name)
+    X = X.detach()
+    if X.dim() == 1:
+        X = X.unsqueeze(1)
+    if X.dim() != 2:
+        raise ValueError(f"{name} must have shape (N,) or (N, K)")
+    N, K = X.shape
+    if K < 1 or K > CALIB_MAX_K:
+        raise _lib.NpldaHipError(f"{name}: {K} systems are outside the compiled kernel set (1 .. {CALIB_MAX_K})")
+    if N > 1 and (X.stride(1) != 1 or X.stride(0) < K):
+        X = X.contiguous()
+    elif N <= 1:
+        X = X.contiguous()
+    return X, N, K, (X.stride(0) if N > 1 else K), sfx
+
+
+def _calib_target(target, N, dev):
+    _require_dev_f32(target, "target")
+    t = target.detach().reshape(-1).contiguous()
+    if t.numel() != N or t.device != dev:
+        raise ValueError("target must hold one label per trial, on the device of the scores")
+    return t
+
+
+def _calib_workspace(lib, N, K, dev):
+    nbytes = lib.nplda_calib_workspace_bytes(N, K)
+    if nbytes == 0:
+        raise _lib.NpldaHipError(f"{N} trials of {K} systems are outside the supported range (N >= 2, K <= {CALIB_MAX_K})")
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=dev), nbytes
+
+
+CALIB_MAX_K = 8
+CALIB_REPORT = ("objective", "grad_inf", "iterations", "passes", "converged", "not_finite", "stalled", "n_tgt", "n_non",
+                "alpha")
+
+
+def calib_logreg_pass(scores, target, theta, p_target=0.5, l2=0.0):
+    """nplda_calib_logreg_pass_*: scores (N,) or (N, K) fp32 / fp64, target (N,) fp32 0/1, theta (K + 1,) fp64 ->
+    (counts (2,) = N_tgt, N_non; J (1,); g (K + 1,); H_upper ((K + 1)(K + 2) / 2,)), device doubles (views of one tensor)."""
+    lib = _lib.load()
+    X, N, K, ldx, sfx = _calib_scores(scores)
+    t = _calib_target(target, N, X.device)
+    _require_dev_f64(theta, "theta", K + 1, X.device)
+    theta = theta.detach().contiguous()
+    ws, nbytes = _calib_workspace(lib, N, K, X.device)
+    nh = (K + 1) * (K + 2) // 2
+    out = torch.empty(3 + K + 1 + nh, dtype=torch.float64, device=X.device)
+    with _lib.on_device(X.device):
+        code = getattr(lib, "nplda_calib_logreg_pass_" + sfx)(_lib.ptr(X), N, ldx, K, _lib.ptr(t), _lib.ptr(theta),
+                                                              float(p_target), float(l2), _lib.ptr(out), _lib.ptr(ws),
+                                                              nbytes, _lib.current_stream())
+    _lib.check(code, "nplda_calib_logreg_pass_" + sfx)
+    return out[:2], out[2:3], out[3:4 + K], out[4 + K:]
+
+
+def calib_logreg_fit(scores, target, theta, p_target=0.5, l2=0.0, max_passes=64, tol=1e-10, chunk=8):
+    """nplda_calib_logreg_fit_*: damped Newton from `theta` ((K + 1,) device fp64, updated IN PLACE to the last accepted
+    value) -> report: (10,) device doubles named by CALIB_REPORT.  chunk=None enqueues the whole budget of max_passes
+    (pass, step) launch pairs at once and never synchronises; chunk=c enqueues c pairs at a time and reads the report in
+    between (one device-to-host copy), so that a fit that converged does not pay for the no-op launches of the rest."""
+    lib = _lib.load()
+    X, N, K, ldx, sfx = _calib_scores(scores)
+    t = _calib_target(target, N, X.device)
+    _require_dev_f64(theta, "theta", K + 1, X.device)
+    if not theta.is_contiguous():
+        raise ValueError("theta is updated in place: it must be contiguous")
+    max_passes = int(max_passes)
+    if not 1 <= max_passes <= 256:
+        raise ValueError("max_passes must be in 1 .. 256")
+    ws, nbytes = _calib_workspace(lib, N, K, X.device)
+    report = torch.empty(len(CALIB_REPORT), dtype=torch.float64, device=X.device)
+    fn = getattr(lib, "nplda_calib_logreg_fit_" + sfx)
+    left, resume = max_passes, 0
+    with _lib.on_device(X.device):
+        while left > 0:
+            n = left if chunk is None else min(int(chunk), left)
+            code = fn(_lib.ptr(X), N, ldx, K, _lib.ptr(t), _lib.ptr(theta), float(p_target), float(l2), n, float(tol),
+                      resume, _lib.ptr(report), _lib.ptr(ws), nbytes, _lib.current_stream())
+            _lib.check(code, "nplda_calib_logreg_fit_" + sfx)
+            left -= n
+            resume = 1
+            if left > 0 and bool(report[4:7].any().item()):  # converged, not finite or stalled
+                break
+    return report
+
+
+def calib_gauss_fit(scores, target):
+    """nplda_calib_gauss_fit_*: (N,) scores fp32 / fp64, target (N,) fp32 0/1 -> (6,) device doubles: count, mean, population
+    standard deviation of the targets, then of the non-targets."""
+    lib = _lib.load()
+    sfx = _require_dev_float(scores, "scores")
+    s = scores.detach().reshape(-1).contiguous()
+    N = s.numel()
+    t = _calib_target(target, N, s.device)
+    ws, nbytes = _calib_workspace(lib, N, 1, s.device)
+    out = torch.empty(6, dtype=torch.float64, device=s.device)
+    with _lib.on_device(s.device):
+        code = getattr(lib, "nplda_calib_gauss_fit_" + sfx)(_lib.ptr(s), _lib.ptr(t), N, _lib.ptr(out), _lib.ptr(ws), nbytes,
+                                                            _lib.current_stream())
+    _lib.check(code, "nplda_calib_gauss_fit_" + sfx)
+    return out
+
+
+def calib_apply_linear(scores, theta, out_dtype=torch.float64):
+    """nplda_calib_apply_linear_*: scores (N,) or (N, K), theta (K + 1,) device fp64 -> (N,) of out_dtype (fp32 / fp64)."""
+    lib = _lib.load()
+    X, N, K, ldx, sfx = _calib_scores(scores)
+    _require_dev_f64(theta, "theta", K + 1, X.device)
+    if out_dtype not in (torch.float32, torch.float64):
+        raise TypeError("out_dtype must be float32 or float64")
+    theta = theta.detach().contiguous()
+    out = torch.empty(N, dtype=out_dtype, device=X.device)
+    with _lib.on_device(X.device):
+        code = getattr(lib, "nplda_calib_apply_linear_" + sfx)(_lib.ptr(X), N, ldx, K, _lib.ptr(theta), _lib.ptr(out),
+                                                               int(out_dtype == torch.float64), _lib.current_stream())
+    _lib.check(code, "nplda_calib_apply_linear_" + sfx)
+    return out
+
+
+def calib_apply_gauss(scores, mu_tgt, std_tgt, mu_imp, std_imp, out_dtype=torch.float64):
+    """nplda_calib_apply_gauss_*: the difference of the two normal log densities at every score (any shape, kept)."""
+    lib = _lib.load()
+    sfx = _require_dev_float(scores, "scores")
+    if out_dtype not in (torch.float32, torch.float64):
+        raise TypeError("out_dtype must be float32 or float64")
+    s = scores.detach().contiguous()
+    out = torch.empty(s.shape, dtype=out_dtype, device=s.device)
+    with _lib.on_device(s.device):
+        code = getattr(lib, "nplda_calib_apply_gauss_" + sfx)(_lib.ptr(s), s.numel(), float(mu_tgt), float(std_tgt),
+                                                              float(mu_imp), float(std_imp), _lib.ptr(out),
+                                                              int(out_dtype == torch.float64), _lib.current_stream())
+    _lib.check(code, "nplda_calib_apply_gauss_" + sfx)
+    return out
+
+
+def calib_costs(llr, target, thresholds=()):
+    """nplda_calib_costs_*: llr (N,) fp32 / fp64, target (N,) fp32 0/1, up to 8 thresholds (floats, +-inf allowed) ->
+    (counts (2,) int64 = N_tgt, N_non; miss (nth,) int64; fa (nth,) int64; cllr_sums (2,) fp64 in bits), on the device."""
+    lib = _lib.load()
+    sfx = _require_dev_float(llr, "llr")
+    s = llr.detach().reshape(-1).contiguous()
+    N = s.numel()
+    t = _calib_target(target, N, s.device)
+    nth = len(thresholds)
+    if nth > 8:
+        raise _lib.NpldaHipError("at most 8 thresholds per call")
+    ws, nbytes = _calib_workspace(lib, max(N, 2), 1, s.device)
+    counts = torch.empty(2 + 2 * nth, dtype=torch.int64, device=s.device)
+    sums = torch.empty(2, dtype=torch.float64, device=s.device)
+    tarr = (ctypes.c_double * max(nth, 1))(*[float(v) for v in thresholds])
+    with _lib.on_device(s.device):
+        code = getattr(lib, "nplda_calib_costs_" + sfx)(_lib.ptr(s), _lib.ptr(t), N, tarr, nth, _lib.ptr(counts),
+                                                        _lib.ptr(sums), _lib.ptr(ws), nbytes, _lib.current_stream())
+    _lib.check(code, "nplda_calib_costs_" + sfx)
+    return counts[:2], counts[2:2 + nth], counts[2 + nth:], sums
