@@ -570,7 +570,8 @@ int nplda_text_column_spans(const char* text, size_t len, int64_t skip_rows, int
  * numel are HOST arrays of nseg entries (device pointers / element counts).  step: DEVICE buffer of TWO 4-byte words,
  * zero-initialised by the caller: step[0] is the number of steps taken so far as a float (incremented by the launch,
  * the new value is the one used for the bias correction), step[1] is scratch of the launch (an arrival counter, zero
- * between launches).  Graph-replay safe: nothing about the step lives on the host. */
+ * between launches).  Graph-replay safe: nothing about the step lives on the host.  A segment of numel == 0 may carry
+ * null pointers (a tensor without storage has none); a launch whose segments are all empty only counts the step. */
 int nplda_adam_step_f32(float* const* params, const float* const* grads, float* const* exp_avg,
                         float* const* exp_avg_sq, const int64_t* numel, int nseg, float* step, float lr,
                         float beta1, float beta2, float eps, float weight_decay, nplda_stream_t stream);

@@ -63,7 +63,9 @@ int nplda_adam_step_f32(float* const* params, const float* const* grads, float* 
     AdamArgs a = {};
     a.nseg = nseg;
     for (int i = 0; i < nseg; ++i) {
-        if (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i] || numel[i] < 0) return NPLDA_EINVAL;
+        if (numel[i] < 0) return NPLDA_EINVAL;
+        // (a zero-element tensor has no storage: torch hands out null pointers for it, and no thread maps to the segment)
+        if (numel[i] > 0 && (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i])) return NPLDA_EINVAL;
         a.seg[i] = AdamSeg{params[i], grads[i], exp_avg[i], exp_avg_sq[i], (long long)numel[i]};
         a.total += numel[i];
     }
