@@ -204,6 +204,39 @@ int nplda_score_embeddings_bwd_f32(const float* z1, int64_t ld1, const float* z2
                                    float* dz2, int64_t ldd2, float* dP_sqrt, float* dQ, void* ws, size_t ws_bytes,
                                    nplda_stream_t stream);
 
+/* ---- all-pairs training step on a batch of embeddings (csrc/nplda_allpairs.hip, design/k17_allpairs.md) ---------- */
+
+/* Rows of z one block of the all-pairs kernel owns (tests place their ragged edges by it). */
+#define NPLDA_ALLPAIRS_TILE 64
+
+/* Bytes of caller-provided workspace nplda_allpairs_loss_f32 needs for N rows of D2 features and K thresholds (the padded
+ * image of z, the self terms, the per-block partial sums).  0 for N < 0, N > 2^20, D2 above nplda_max_dim() or K outside
+ * 1..4. */
+size_t nplda_allpairs_workspace_bytes(int64_t N, int D2, int K);
+
+/* The loss over ALL trials a batch of N embeddings implies, with every gradient: what the reference computes by listing
+ * the pairs (utils/sv_trials_loaders.py:22-75, TrialSampler), scoring each (utils/models.py:372-376) and taking the loss
+ * (utils/models.py:384-399) and its autograd, each utterance embedded once per pair it appears in.  Here
+ *   T = {(i, j): i < j, and grp[i] == grp[j] when grp != NULL}, a trial is a target iff spk[i] == spk[j],
+ *   s_ij = q_i + q_j + 2 sum_d P_d z_id z_jd,  q_i = sum_d Q_d z_id^2,  P = P_sqrt^2,
+ *   sums (nplda_loss_nsums doubles), loss and dtheta as nplda_loss_fwd_bwd_f32 gives them on the scores of T (the BCE
+ *   normaliser is |T|; N_t and N_n are counted exactly from the labels), and with g_ij = dL/ds_ij, G symmetric with
+ *   G_ij = G_ji = g_ij on T and 0 elsewhere, r_i = sum_j G_ij, A_i = sum_j G_ij z_j:
+ *   dz_i = 2 r_i (Q o z_i) + 2 P o A_i,  dQ_d = sum_i r_i z_id^2,  dP_sqrt_d = 2 P_sqrt_d sum_i z_id A_id
+ *   (= 4 P_sqrt sum_{i<j} g z_i z_j, as nplda_score_embeddings_bwd_f32 defines it).
+ * The N x N matrices are never written.  z: (N, ldz); spk, grp: N int32 (grp may be NULL: one group); theta: HOST array of K
+ * device pointers, beta: HOST array of K floats (NULL for BCE), as for nplda_loss_fwd_bwd_f32; kind 0 = SoftCdet, 1 = BCE
+ * (theta[0]).  dz (N, lddz), dP_sqrt (D2), dQ (D2) and dtheta (K) may each be NULL; with all three gradients NULL only the
+ * tiles that hold a trial are walked.  Kernel launches on `stream` and nothing else (no allocation, no memset, no
+ * synchronisation: capturable); bitwise repeatable (fixed summation orders, no floating-point atomics).  N < 2 or an empty T:
+ * sums and gradients 0, loss 0 / 0.  NPLDA_EINVAL: a null required pointer, N < 0, D2 <= 0, K outside 1..4, kind outside
+ * {0, 1}, z / dz / ws not 16-byte aligned or ldz / lddz not a multiple of 4 or below D2; NPLDA_EUNSUPPORTED: D2 above
+ * nplda_max_dim() or N above 2^20; NPLDA_ENOSPC: ws_bytes below nplda_allpairs_workspace_bytes(N, D2, K). */
+int nplda_allpairs_loss_f32(const float* z, int64_t ldz, int64_t N, int D2, const int32_t* spk, const int32_t* grp,
+                            const float* P_sqrt, const float* Q, const float* const* theta, const float* beta, int K,
+                            float alpha, int kind, double* sums, float* loss, float* dtheta, float* dz, int64_t lddz,
+                            float* dP_sqrt, float* dQ, void* ws, size_t ws_bytes, nplda_stream_t stream);
+
 /* ---- small resident-matrix GEMM on row batches (input gradients; csrc/nplda_matmul.hip) ---------------------- */
 
 /* MFMA-fragment image of a K x N matrix Wm (K <= 512, N % 4 == 0) for nplda_rows_matmul_f32.  mode 0: Wm = src (K, N)

@@ -351,6 +351,38 @@ class _LossFn(torch.autograd.Function):
         return (_back(gg, output) if ctx.needs_input_grad[0] else None, None, None, None, None, None) + tuple(dths)
 
 
+class _AllPairsLossFn(torch.autograd.Function):
+    """SoftCdet / BCE over every trial (i < j, same group) among the embeddings z (N, D2) with speaker labels `spk` —
+    the pairs TrialSampler lists one by one (utils/sv_trials_loaders.py:22-75), from N embeddings instead of 2 |T|.  The
+    gradients of z, P_sqrt, Q and the thresholds come out of the forward's one pass (ops.allpairs_loss) and are scaled by
+    the incoming gradient in backward, as _LossFn's joint form does."""
+
+    @staticmethod
+    def forward(ctx, z, spk, grp, kind, alpha, betas, opts, P_sqrt, Q, *thetas):
+        (grad_on,) = opts
+        dev = _compute_device(z, Q)
+        Z, ps, q = _to_dev(z, dev), _to_dev(P_sqrt, dev), _to_dev(Q, dev)
+        ths = [_to_dev(th, dev) for th in thetas]
+        need = grad_on and (ctx.needs_input_grad[0] or any(ctx.needs_input_grad[7:]))
+        loss, dth, _, dz, dP, dQ = ops.allpairs_loss(Z, spk, ps, q, ths, betas, alpha, kind, grp=grp, want_grad=need)
+        ctx.need, ctx.nth = need, len(thetas)
+        if need:
+            ctx.save_for_backward(dz, dP, dQ, dth, z, P_sqrt, Q, *thetas)
+        return loss if loss.device == z.device else loss.to(z.device)
+
+    @staticmethod
+    def backward(ctx, gl):
+        if not ctx.need:
+            return (None,) * (9 + ctx.nth)
+        dz, dP, dQ, dth, z, P_sqrt, Q = ctx.saved_tensors[:7]
+        thetas = ctx.saved_tensors[7:]
+        gl = gl.to(dz.device)
+        need = ctx.needs_input_grad
+        dths = [_back(dth[k:k + 1] * gl, th) if nd else None for k, (th, nd) in enumerate(zip(thetas, need[9:]))]
+        return (_back(dz * gl, z) if need[0] else None, None, None, None, None, None, None,
+                _back(dP * gl, P_sqrt) if need[7] else None, _back(dQ * gl, Q) if need[8] else None) + tuple(dths)
+
+
 # ---------------------------------------------------------------------------------------------------
 # NeuralPlda
 # ---------------------------------------------------------------------------------------------------
@@ -502,6 +534,25 @@ class NeuralPlda(nn.Module):
             return self.softcdet(output, target)
         return self.crossentropy(output, target)
 
+    def loss_all_pairs(self, x, speakers, groups=None):
+        """The model's loss (`lossfn`) over every trial among the utterances of a batch: x (N, D0) x-vectors (for
+        Etdnn_Xvec_NeuralPlda: whatever its extract_plda_embeddings takes), `speakers` one integer label per utterance,
+        `groups` (optional) one label per utterance for utterances that must not be paired across groups (one gender or
+        source per spk2utt list).  Trials are the pairs i < j of one group, targets those of one speaker: N (N - 1) / 2
+        trials for N embeddings (and N extractions), where forward(x1, x2) embeds both sides of every pair.  `speakers`
+        and `groups`: integer tensors on any device, or sequences of ints."""
+        if self._reduce_flat is not None or self._reduce_sums is not None:
+            raise NotImplementedError("loss_all_pairs on a data-parallel model: all pairs across ranks need an "
+                                      "all-gather of the embeddings, which is not implemented")
+        z = self.extract_plda_embeddings(x)
+        opts = (torch.is_grad_enabled(),)
+        if _loss_kind(self.lossfn) == ops.LOSS_SOFTCDET:
+            thetas = [self.threshold[b] for b in self.beta]
+            return _AllPairsLossFn.apply(z, speakers, groups, ops.LOSS_SOFTCDET, self._alpha(),
+                                         [float(b) for b in self.beta], opts, self.P_sqrt, self.Q, *thetas)
+        return _AllPairsLossFn.apply(z, speakers, groups, ops.LOSS_BCE, 0.0, [], opts, self.P_sqrt, self.Q,
+                                     self.threshold_Xent)
+
     def cdet(self, output, target):
         """utils/models.py:401-404: hard detection cost at the model thresholds (strict < / >)."""
         dev = _compute_device(output, target)
@@ -622,6 +673,9 @@ class DPlda(NeuralPlda):
         """utils/models.py:503-506: BCE(sigmoid(output), target) — no threshold."""
         zero = torch.zeros(1, dtype=torch.float32, device=output.device)
         return _LossFn.apply(output, target, ops.LOSS_BCE, 0.0, [], (self._reduce_sums, torch.is_grad_enabled()), zero)
+
+    def loss_all_pairs(self, x, speakers, groups=None):
+        raise NotImplementedError("loss_all_pairs covers the NeuralPlda score (P_sqrt, Q); DPlda has a quadratic-form head")
 
     def LoadParamsFromKaldi(self, mean_vec_file, transform_mat_file):
         """utils/models.py:551-564."""

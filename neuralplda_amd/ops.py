@@ -516,6 +516,77 @@ def loss_joint_views(joint, B, K):
     return joint[:B], joint[o:o + K]
 
 
+ALLPAIRS_TILE = 64  # rows of z one block of the all-pairs kernel owns (NPLDA_ALLPAIRS_TILE, include/nplda_hip.h)
+
+
+def _labels(t, name, N, dev):
+    """Integer labels (a tensor on any device, or a sequence of ints) -> contiguous int32 (N,) on `dev`."""
+    if not isinstance(t, torch.Tensor):
+        t = torch.as_tensor(t)
+        if t.numel() == 0:  # (an empty sequence has no dtype of its own)
+            t = t.to(torch.int32)
+    if t.is_floating_point() or t.dtype == torch.bool or t.is_complex():
+        raise TypeError(f"{name} must be integer labels (got {t.dtype})")
+    if t.dim() != 1 or t.shape[0] != N:
+        raise ValueError(f"{name} must be one label per row of z: ({N},), got {tuple(t.shape)}")
+    if t.dtype != torch.int32:
+        t = t.to(torch.int32)
+    if t.device != dev:
+        t = t.to(dev, non_blocking=True)
+    return t.contiguous()
+
+
+def allpairs_loss(z, spk, P_sqrt, Q, thetas, betas, alpha, kind, grp=None, want_grad=True):
+    """nplda_allpairs_loss_f32: the loss over every trial (i < j, same group) of the batch z (N, D2) with speaker labels
+    spk (N,) -> (loss 0-d, dtheta (K,) or None, sums fp64, dz (N, D2) or None, dP_sqrt (D2) or None, dQ (D2) or None).
+    The N x N scores are never materialised; want_grad=False computes the loss and the sums only."""
+    lib = _lib.load()
+    for n, t in (("z", z), ("P_sqrt", P_sqrt), ("Q", Q)):
+        _require_dev_f32(t, n)
+    D2 = Q.numel()
+    if z.dim() != 2 or z.shape[1] != D2 or P_sqrt.numel() != D2:
+        raise ValueError(f"z must be (N, {D2}) and P_sqrt ({D2},)")
+    if kind not in (LOSS_SOFTCDET, LOSS_BCE):
+        raise _lib.NpldaHipError("allpairs_loss: the loss is SoftCdet or BCE")
+    N, dev = z.shape[0], z.device
+    K = len(thetas)
+    ld = (D2 + 3) & ~3
+    if not (z.stride(1) == 1 and z.stride(0) >= D2 and z.stride(0) % 4 == 0 and z.data_ptr() % 16 == 0) and N > 0:
+        zb = torch.empty((N, ld), dtype=torch.float32, device=dev)  # 16-byte aligned rows; columns >= D2 are never read
+        zb[:, :D2] = z
+        z = zb
+    spk = _labels(spk, "spk", N, dev)
+    grp = None if grp is None else _labels(grp, "grp", N, dev)
+    wsb = lib.nplda_allpairs_workspace_bytes(N, D2, K)
+    ns = lib.nplda_loss_nsums(K, kind)
+    if wsb == 0 or ns == 0:
+        raise _lib.NpldaHipError(f"allpairs_loss: N = {N}, D2 = {D2}, K = {K} is outside the compiled kernel set")
+    ws = torch.empty(wsb // 4, dtype=torch.float32, device=dev)
+    sums = torch.empty(ns, dtype=torch.float64, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    dth = dzb = dP = dQ = None
+    if want_grad:
+        dth = torch.empty(K, dtype=torch.float32, device=dev)
+        dzb = torch.empty((N, ld), dtype=torch.float32, device=dev)
+        dP = torch.empty(D2, dtype=torch.float32, device=dev)
+        dQ = torch.empty(D2, dtype=torch.float32, device=dev)
+    _, tharr, barr, _ = _step_consts(None, thetas, betas, kind)
+    with _lib.on_device(dev):
+        code = lib.nplda_allpairs_loss_f32(_lib.ptr(z), z.stride(0) if N > 1 else ld, N, D2, _lib.ptr(spk), _lib.ptr(grp),
+                                           _lib.ptr(P_sqrt.contiguous()), _lib.ptr(Q.contiguous()), tharr, barr, K,
+                                           float(alpha), kind, _lib.ptr(sums), _lib.ptr(loss), _lib.ptr(dth),
+                                           _lib.ptr(dzb), ld, _lib.ptr(dP), _lib.ptr(dQ), _lib.ptr(ws), wsb,
+                                           _lib.current_stream())
+    _lib.check(code, "nplda_allpairs_loss_f32")
+    if N == 0:  # the call is a no-op there: the formulas on an empty trial set
+        sums.zero_()
+        loss.fill_(float("nan"))
+        for t in (dth, dzb, dP, dQ):
+            if t is not None:
+                t.zero_()
+    return loss, dth, sums, (dzb[:, :D2] if want_grad else None), dP, dQ
+
+
 def pack_params_into(packed, W1, b1, W2, b2, P_sqrt, Q):
     """nplda_pack_params_f32 into an EXISTING PackedParams buffer (its address is baked into captured graphs)."""
     lib = _lib.load()

@@ -20,7 +20,7 @@ import torch
 from torch.utils.data import DataLoader, Dataset
 
 __all__ = ["combine_trials_and_get_loader", "get_trials_loaders_dict", "load_xvec_trials_from_numbatch",
-           "load_xvec_trials_from_idbatch", "XvectorTable", "xvector_table", "TrialIndexDataset"]
+           "load_xvec_trials_from_idbatch", "XvectorTable", "xvector_table", "TrialIndexDataset", "SpeakerBatchLoader"]
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -529,3 +529,108 @@ def load_xvec_trials_from_idbatch(mega_dict, trials, device):
         return e, e.clone()
     trials = trials.reshape(-1, trials.shape[-1])
     return (tab.gather(_ids_to_rows(tab, trials[:, 0]), device), tab.gather(_ids_to_rows(tab, trials[:, 1]), device))
+
+
+# ---------------------------------------------------------------------------------------------------
+# per-utterance batches for NeuralPlda.loss_all_pairs
+# ---------------------------------------------------------------------------------------------------
+
+class SpeakerBatchLoader:
+    """Per-utterance counterpart of TrialSampler (utils/sv_trials_loaders.py:22-75): where the reference picks a few
+    speakers, a chunk of utterances for each and LISTS the target / non-target trials among them, this yields the
+    utterances themselves, `(rows, spk, grp)` — table rows (for `table.gather` / `table.on(dev)[rows]`), one integer speaker
+    label and one integer group label per row (`grp` is None without `groups`) — and NeuralPlda.loss_all_pairs forms
+    every trial of the batch on the device.
+
+    Per epoch each speaker's utterances that the table holds are shuffled and cut into consecutive chunks of
+    `utts_per_speaker`; a last chunk of at least 2 is kept, a single left-over utterance is dropped.  A batch takes the next
+    chunk of `speakers_per_batch` distinct speakers (drawn among those that still have one); the epoch ends when fewer
+    speakers than that have a chunk left.  No utterance appears twice in an epoch.  Host-side numpy, deterministic in
+    (seed, epoch): every `iter()` starts the next epoch, `set_epoch(e)` chooses it.
+
+    spk2utt: a Kaldi spk2utt path, a list of such paths, a dict {spk: [utt, ...]} or a list of (spk, [utt, ...]).
+    groups: {spk: group} (speakers it does not name form one more group), or a list of spk2utt paths that are one group each
+    (spk2utt may then be None: their union).  device: yield torch tensors on it (rows int64, labels int32) instead of numpy."""
+
+    def __init__(self, table, spk2utt, speakers_per_batch, utts_per_speaker, groups=None, seed=0, device=None):
+        from . import backend
+        if speakers_per_batch < 1 or utts_per_speaker < 1:
+            raise ValueError("speakers_per_batch and utts_per_speaker must be positive")
+        group_of = {}
+        if groups is not None and not isinstance(groups, dict):
+            lists = [backend.read_spk2utt(p) for p in groups]
+            for k, lst in enumerate(lists):
+                for s, _ in lst:
+                    group_of.setdefault(s, k)
+            if spk2utt is None:
+                spk2utt = [e for lst in lists for e in lst]
+        elif groups is not None:
+            names = {}
+            for s, gname in groups.items():
+                group_of[s] = names.setdefault(gname, len(names))
+        if isinstance(spk2utt, (str, os.PathLike)):
+            spk2utt = backend.read_spk2utt(spk2utt)
+        elif isinstance(spk2utt, dict):
+            spk2utt = list(spk2utt.items())
+        elif spk2utt and isinstance(spk2utt[0], (str, os.PathLike)):
+            spk2utt = [e for p in spk2utt for e in backend.read_spk2utt(p)]
+        if spk2utt is None:
+            raise ValueError("spk2utt is required unless `groups` lists the spk2utt files")
+        row_of = table.row_of
+        merged = {}
+        for s, utts in spk2utt:
+            merged.setdefault(s, []).extend(utts)
+        self.speakers, self._rows, self.missing = [], [], []
+        for s, utts in merged.items():
+            rows = []
+            for u in dict.fromkeys(utts):
+                r = row_of.get(u)
+                if r is None:
+                    self.missing.append(u)
+                else:
+                    rows.append(r)
+            if rows:
+                self.speakers.append(s)
+                self._rows.append(np.asarray(rows, dtype=np.int64))
+        other = (max(group_of.values()) + 1) if group_of else 0
+        self._group = None if groups is None else np.asarray([group_of.get(s, other) for s in self.speakers], dtype=np.int32)
+        self.speakers_per_batch, self.utts_per_speaker = int(speakers_per_batch), int(utts_per_speaker)
+        self.seed, self.epoch, self.device = int(seed), 0, device
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def _chunks(self, rng):
+        """Per speaker: this epoch's list of row chunks."""
+        U, out = self.utts_per_speaker, []
+        for rows in self._rows:
+            perm = rows[rng.permutation(rows.size)]
+            cut = [perm[o:o + U] for o in range(0, perm.size, U)]
+            if cut and cut[-1].size < min(U, 2):
+                cut.pop()
+            out.append(cut)
+        return out
+
+    def __iter__(self):
+        rng = np.random.default_rng([self.seed, self.epoch])
+        self.epoch += 1
+        chunks = self._chunks(rng)
+        nxt = np.zeros(len(chunks), dtype=np.int64)
+        left = np.asarray([len(c) for c in chunks], dtype=np.int64)
+        S = self.speakers_per_batch
+        while True:
+            have = np.flatnonzero(left > 0)
+            if have.size < S:
+                return
+            pick = np.sort(rng.permutation(have)[:S])
+            rows = [chunks[s][nxt[s]] for s in pick]
+            nxt[pick] += 1
+            left[pick] -= 1
+            spk = np.concatenate([np.full(r.size, s, dtype=np.int32) for s, r in zip(pick, rows)])
+            rows = np.concatenate(rows)
+            grp = None if self._group is None else self._group[spk]
+            if self.device is not None:
+                rows = torch.from_numpy(rows).to(self.device)
+                spk = torch.from_numpy(spk).to(self.device)
+                grp = None if grp is None else torch.from_numpy(grp).to(self.device)
+            yield rows, spk, grp
