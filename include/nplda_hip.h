@@ -547,6 +547,50 @@ int nplda_calib_costs_f32(const float* llr, const float* target, int64_t N, cons
 int nplda_calib_costs_f64(const double* llr, const float* target, int64_t N, const double* thresholds, int nth,
                           int64_t* counts, double* sums, void* workspace, size_t workspace_bytes, nplda_stream_t stream);
 
+/* ---- PAV / ROC convex hull: min Cllr, ROCCH EER, isotonic calibration (csrc/nplda_pav.hip) ----------------------- */
+
+/* The isotonic regression of the labels on the scores, as the strict lower convex hull of the cumulative (trials,
+ * targets) diagram of the score bins (design/k18_pav_rocch.md).  scores: N fp32 (_f32) or fp64 (_f64); target as above
+ * (neither class: the trial is excluded); a trial whose score is NaN is excluded too, +-inf are scores.  Equal scores
+ * (==) form one bin.  laplace != 0 adds a bin (n = 2, t = 1) at -inf and one at +inf before the hull.
+ * Block table, DEVICE arrays of `cap` >= 1 entries: lo, hi (first and last score of the block's real bins; a block made
+ * of a dummy bin alone has lo = hi = -+inf), n, t (trials and targets, dummy trials included) and
+ * llr = log(t / (n - t)) - log(N_t' / N_n') with N' the class counts (+ 2 each under the Laplace rule).
+ * summary, 8 DEVICE doubles: N_t, N_n (real trials kept), M (bins), nb (blocks: always the true number), min Cllr and
+ * the ROCCH equal error rate of THIS block table (NaN when a class is empty), an overflow flag (nb > cap: the blocks
+ * beyond cap were not written), 0.
+ * Everything is enqueued on `stream`; nothing is read back and the number of launches depends on N only; the result is
+ * bitwise repeatable (integer hull decisions, fixed-order fp64 sums).
+ * A null pointer, a pointer that is not aligned to its type (workspace: 16 bytes), N < 2 or cap < 1 -> NPLDA_EINVAL;
+ * N >= 2^31 -> NPLDA_EUNSUPPORTED; workspace_bytes < nplda_pav_workspace_bytes(N, is_f64) -> NPLDA_ENOSPC; all before
+ * anything is enqueued.  nplda_pav_workspace_bytes needs no device, returns 0 for N < 2 or N >= 2^31 and does not
+ * decrease with N. */
+int nplda_pav_chunk(void); /* points one thread scans at level 0 of the hull: tests straddle its multiples */
+size_t nplda_pav_workspace_bytes(int64_t N, int is_f64);
+int nplda_pav_fit_f32(const float* scores, const float* target, int64_t N, int laplace, double* lo, double* hi, int64_t* n,
+                      int64_t* t, double* llr, int64_t cap, double* summary, void* workspace, size_t workspace_bytes,
+                      nplda_stream_t stream);
+int nplda_pav_fit_f64(const double* scores, const float* target, int64_t N, int laplace, double* lo, double* hi, int64_t* n,
+                      int64_t* t, double* llr, int64_t cap, double* summary, void* workspace, size_t workspace_bytes,
+                      nplda_stream_t stream);
+
+/* For stage timing (tools/bench_pav.py): nplda_pav_fit_f32 cut short after the sort and scan (stop_after = 1), the
+ * binning (2) or the hull (3); 0 runs everything.  Outputs are written by the full run only. */
+int nplda_pav_fit_stages_f32(const float* scores, const float* target, int64_t N, int laplace, double* lo, double* hi,
+                             int64_t* n, int64_t* t, double* llr, int64_t cap, double* summary, void* workspace,
+                             size_t workspace_bytes, int stop_after, nplda_stream_t stream);
+
+/* out_i = the table's llr at scores_i: llr_b inside a block (lo_b <= s <= hi_b, the first such block), the first / last
+ * block's beyond the ends, linear in s across a gap with two finite ends (clamped to [llr_b, llr_b+1]; an infinite llr
+ * at either end of the gap is taken as it is, the left one first), the llr of the block on the infinite side of a gap
+ * with one infinite end, NaN for NaN.  lo, hi, llr: nb >= 1 DEVICE doubles; out: N floats (out_f64 = 0) or doubles.
+ * N < 0, nb < 1, a null or misaligned pointer -> NPLDA_EINVAL; N or nb >= 2^31 -> NPLDA_EUNSUPPORTED; N = 0 does
+ * nothing. */
+int nplda_pav_apply_f32(const float* scores, int64_t N, const double* lo, const double* hi, const double* llr, int64_t nb,
+                        void* out, int out_f64, nplda_stream_t stream);
+int nplda_pav_apply_f64(const double* scores, int64_t N, const double* lo, const double* hi, const double* llr, int64_t nb,
+                        void* out, int out_f64, nplda_stream_t stream);
+
 /* ---- host-side text I/O of the trial-list path (no device work; plain host pointers) ------------------------------ */
 
 /* Rows and columns of a whitespace-separated table held in memory, with np.genfromtxt(dtype=str) semantics (the

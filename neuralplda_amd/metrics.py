@@ -16,6 +16,12 @@ log-likelihood ratios instead of arbitrary scores:
 * act_cost(llr, target, betas): P_miss + beta * P_fa at the Bayes threshold log(beta) — the cost, beta convention
   (NpldaConf's `beta`) and normalisation of minc_exact, whose minimum over thresholds it can only exceed.
 * act_dcf(llr, target, p_target, c_miss, c_fa): the same counts in NIST's normalisation.
+
+Calibration-insensitive counterparts on the ROC convex hull (kernels nplda_pav_*, csrc/nplda_pav.hip,
+design/k18_pav_rocch.md), for arbitrary scores:
+
+* min_cllr(scores, target): the Cllr of the best monotone map of the scores (PAV); cllr - min_cllr is the calibration loss.
+* rocch_eer(scores, target): the equal error rate on the ROC convex hull; rocch(scores, target): the hull's vertices.
 """
 import math
 
@@ -23,7 +29,7 @@ import torch
 
 from . import _lib, ops
 
-__all__ = ["minc", "eer", "minc_exact", "cllr", "act_cost", "act_dcf"]
+__all__ = ["minc", "eer", "minc_exact", "cllr", "act_cost", "act_dcf", "min_cllr", "rocch_eer", "rocch"]
 
 
 def _on_device(output, target):
@@ -118,3 +124,57 @@ def act_dcf(llr, target, p_target, c_miss=1.0, c_fa=1.0):
     wm, wf = c_miss * p_target, c_fa * (1.0 - p_target)
     nt, nn, miss, fa, _ = _rates(llr, target, [math.log(wf / wm)])
     return (wm * miss[0] / nt + wf * fa[0] / nn) / min(wm, wf)
+
+
+def _hull(scores, target):
+    """One nplda_pav_fit_* call without the Laplace rule -> (n, t) of the blocks (device int64) and the summary as a dict."""
+    s, t = _llr_on_device(scores, target)
+    if s.numel() < 2:
+        raise ValueError("the metric needs trials of both classes")
+    cap = None
+    for _ in range(2):
+        _, _, n, tt, _, summary = ops.pav_fit(s, t, laplace=False, cap=cap)
+        rep = dict(zip(ops.PAV_SUMMARY, summary.tolist()))
+        if rep["n_tgt"] < 1 or rep["n_non"] < 1:
+            raise ValueError(f"the metric needs trials of both classes (got {int(rep['n_tgt'])} targets, "
+                             f"{int(rep['n_non'])} non-targets)")
+        if not rep["overflow"]:
+            break
+        cap = int(rep["blocks"])  # the true number is always reported: the second call fits
+    nb = int(rep["blocks"])
+    return n[:nb], tt[:nb], rep
+
+
+def min_cllr(scores, target):
+    """Cllr, in bits, after the optimal monotone (PAV) map of the scores: a float.  Trials whose score is NaN are ignored."""
+    s, t = _llr_on_device(scores, target)
+    if s.numel() < 2:
+        raise ValueError("the metric needs trials of both classes")
+    rep = dict(zip(ops.PAV_SUMMARY, ops.pav_fit(s, t, laplace=False, cap=1)[5].tolist()))  # the table is not wanted
+    if rep["n_tgt"] < 1 or rep["n_non"] < 1:
+        raise ValueError(f"the metric needs trials of both classes (got {int(rep['n_tgt'])} targets, "
+                         f"{int(rep['n_non'])} non-targets)")
+    return rep["min_cllr"]
+
+
+def rocch_eer(scores, target):
+    """Equal error rate on the ROC convex hull (P_miss = P_fa on the hull's edge that crosses the diagonal): a float."""
+    s, t = _llr_on_device(scores, target)
+    if s.numel() < 2:
+        raise ValueError("the metric needs trials of both classes")
+    rep = dict(zip(ops.PAV_SUMMARY, ops.pav_fit(s, t, laplace=False, cap=1)[5].tolist()))
+    if rep["n_tgt"] < 1 or rep["n_non"] < 1:
+        raise ValueError(f"the metric needs trials of both classes (got {int(rep['n_tgt'])} targets, "
+                         f"{int(rep['n_non'])} non-targets)")
+    return rep["rocch_eer"]
+
+
+def rocch(scores, target):
+    """-> (P_fa, P_miss): float64 numpy arrays over the vertices of the ROC convex hull, from (1, 0) (accept everything)
+    to (0, 1), for a DET / ROC plot."""
+    n, t, rep = _hull(scores, target)
+    n, t = n.cpu().numpy(), t.cpu().numpy()
+    import numpy as np
+    T = np.concatenate(([0], np.cumsum(t))).astype(np.float64)
+    F = np.concatenate(([0], np.cumsum(n - t))).astype(np.float64)
+    return 1.0 - F / rep["n_non"], T / rep["n_tgt"]

@@ -1775,3 +1775,60 @@ def calib_costs(llr, target, thresholds=()):
                                                         _lib.ptr(sums), _lib.ptr(ws), nbytes, _lib.current_stream())
     _lib.check(code, "nplda_calib_costs_" + sfx)
     return counts[:2], counts[2:2 + nth], counts[2 + nth:], sums
+
+
+PAV_SUMMARY = ("n_tgt", "n_non", "bins", "blocks", "min_cllr", "rocch_eer", "overflow", "reserved")
+
+
+def pav_chunk():
+    """Points one thread scans at level 0 of the hull (nplda_pav_chunk)."""
+    return int(_lib.load().nplda_pav_chunk())
+
+
+def pav_fit(scores, target, laplace=True, cap=None):
+    """nplda_pav_fit_*: scores (N,) fp32 / fp64, target (N,) fp32 -> (lo, hi, n, t, llr, summary): the block table of
+    the isotonic regression of the labels on the scores (lo, hi, llr fp64; n, t int64; `cap` entries each, of which the
+    first min(blocks, cap) are written) and summary (8,) device doubles named by PAV_SUMMARY.  Nothing is read back:
+    summary[3] is the true number of blocks and summary[6] tells whether it exceeded cap (default min(N + 2, 65536))."""
+    lib = _lib.load()
+    sfx = _require_dev_float(scores, "scores")
+    s = scores.detach().reshape(-1).contiguous()
+    N = s.numel()
+    t = _calib_target(target, N, s.device)
+    cap = min(N + 2, 1 << 16) if cap is None else int(cap)
+    if cap < 1:
+        raise ValueError("cap must be at least 1")
+    nbytes = lib.nplda_pav_workspace_bytes(N, int(sfx == "f64"))
+    if nbytes == 0:
+        raise _lib.NpldaHipError(f"{N} trials are outside the supported range (2 <= N < 2^31)")
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=s.device)
+    fl = torch.empty(3 * cap + 8, dtype=torch.float64, device=s.device)
+    it = torch.empty(2 * cap, dtype=torch.int64, device=s.device)
+    lo, hi, llr, summary = fl[:cap], fl[cap:2 * cap], fl[2 * cap:3 * cap], fl[3 * cap:]
+    with _lib.on_device(s.device):
+        code = getattr(lib, "nplda_pav_fit_" + sfx)(_lib.ptr(s), _lib.ptr(t), N, 1 if laplace else 0, lo.data_ptr(),
+                                                    hi.data_ptr(), it.data_ptr(), it.data_ptr() + 8 * cap, llr.data_ptr(),
+                                                    cap, summary.data_ptr(), _lib.ptr(ws), nbytes, _lib.current_stream())
+    _lib.check(code, "nplda_pav_fit_" + sfx)
+    return lo, hi, it[:cap], it[cap:], llr, summary
+
+
+def pav_apply(scores, lo, hi, llr, out_dtype=torch.float64):
+    """nplda_pav_apply_*: scores (any shape, kept) fp32 / fp64 through the block table lo, hi, llr ((nb,) device fp64)."""
+    lib = _lib.load()
+    sfx = _require_dev_float(scores, "scores")
+    if out_dtype not in (torch.float32, torch.float64):
+        raise TypeError("out_dtype must be float32 or float64")
+    s = scores.detach().contiguous()
+    nb = lo.numel()
+    for name, x in (("lo", lo), ("hi", hi), ("llr", llr)):
+        _require_dev_f64(x, name, nb, s.device)
+    if nb < 1:
+        raise ValueError("the block table is empty")
+    lo, hi, llr = lo.contiguous(), hi.contiguous(), llr.contiguous()
+    out = torch.empty(s.shape, dtype=out_dtype, device=s.device)
+    with _lib.on_device(s.device):
+        code = getattr(lib, "nplda_pav_apply_" + sfx)(_lib.ptr(s), s.numel(), _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(llr), nb,
+                                                      _lib.ptr(out), int(out_dtype == torch.float64), _lib.current_stream())
+    _lib.check(code, "nplda_pav_apply_" + sfx)
+    return out

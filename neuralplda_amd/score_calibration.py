@@ -10,6 +10,8 @@ densities.  Here:
 * `fit_linear(scores, target, ...)` -> `LinearCalibration` — what the field uses instead: prior-weighted linear logistic
   regression, `llr = sum_k a_k s_k + b`, over one system (calibration) or up to eight (fusion + calibration), a damped
   Newton iteration whose every pass is one fused reduction kernel (nplda_calib_logreg_fit_*, design/k16_calibration.md).
+* `fit_pav(scores, target, laplace=True)` -> `PavCalibration` — the non-parametric alternative: isotonic regression of the
+  labels on the scores (PAV), as the lower convex hull of the cumulative counts (nplda_pav_fit_*, design/k18_pav_rocch.md).
 * `calibrate_scorefile(dev_score_file, dev_key_file, score_file, ...)` — the script body as a file-in / file-out function.
 
 CPU tensors / arrays are moved to the HIP device and results come back where the inputs were; there is no CPU
@@ -23,8 +25,8 @@ import torch
 
 from . import _lib, ops
 
-__all__ = ["GaussianCalibration", "LinearCalibration", "calibrate_train", "calibrate_apply", "fit_linear",
-           "calibrate_scorefile", "labels_to_target"]
+__all__ = ["GaussianCalibration", "LinearCalibration", "PavCalibration", "calibrate_train", "calibrate_apply", "fit_linear",
+           "fit_pav", "calibrate_scorefile", "labels_to_target"]
 
 TARGET_LABELS = ("target", "tgt")        # utils/score_calibration.py:15
 NONTARGET_LABELS = ("nontarget", "imp")  # :16
@@ -223,16 +225,69 @@ def fit_linear(scores, target, p_target=0.5, l2=0.0, max_passes=64, tol=1e-10, i
                              conv)
 
 
+class PavCalibration:
+    """The block table of a PAV fit: block b covers the scores lo[b] .. hi[b] (n[b] trials, t[b] targets, the two dummy
+    trials of the Laplace rule included) and maps them to llr[b]; between blocks the map is linear in the score.  numpy
+    arrays; n_tgt, n_non are the class counts of the trials the fit kept."""
+    __slots__ = ("lo", "hi", "llr", "n", "t", "laplace", "n_tgt", "n_non", "bins")
+
+    def __init__(self, lo, hi, llr, n, t, laplace=True, n_tgt=0, n_non=0, bins=0):
+        self.lo, self.hi, self.llr = (np.asarray(x, dtype=np.float64).reshape(-1) for x in (lo, hi, llr))
+        self.n, self.t = (np.asarray(x, dtype=np.int64).reshape(-1) for x in (n, t))
+        if not (self.lo.size == self.hi.size == self.llr.size == self.n.size == self.t.size >= 1):
+            raise ValueError("lo, hi, llr, n and t must hold one entry per block, at least one")
+        self.laplace, self.n_tgt, self.n_non, self.bins = bool(laplace), int(n_tgt), int(n_non), int(bins)
+
+    def apply(self, scores, out_dtype=torch.float64):
+        dev = _device(scores)
+        s = _scores_to(scores, dev)
+        if s.numel() == 0:
+            return _back(torch.empty(s.shape, dtype=out_dtype, device=dev), scores)
+        lo, hi, llr = (torch.from_numpy(x).to(dev) for x in (self.lo, self.hi, self.llr))
+        return _back(ops.pav_apply(s, lo, hi, llr, out_dtype=out_dtype), scores)
+
+    def __repr__(self):
+        return (f"PavCalibration({self.llr.size} blocks over {self.bins} bins, laplace={self.laplace}, "
+                f"llr {self.llr[0]:.4f} .. {self.llr[-1]:.4f})")
+
+
+def fit_pav(scores, target, laplace=True):
+    """Isotonic (PAV) calibration: the monotone map of the scores to log-likelihood ratios that minimises Cllr on the
+    data.  laplace=True adds one target and one non-target at each of -inf and +inf, which keeps the end blocks finite.
+    Trials with a NaN score or a label that is neither class are ignored.  Raises ValueError without both classes."""
+    dev = _device(scores, target)
+    s = _scores_to(scores, dev).reshape(-1)
+    t = labels_to_target(target, dev)
+    if s.numel() != t.numel():
+        raise ValueError("one label per score")
+    if s.numel() < 2:
+        raise ValueError("calibration needs trials of both classes")
+    cap = None
+    for _ in range(2):
+        lo, hi, n, tt, llr, summary = ops.pav_fit(s, t, laplace=laplace, cap=cap)
+        rep = dict(zip(ops.PAV_SUMMARY, summary.tolist()))
+        if rep["n_tgt"] < 1 or rep["n_non"] < 1:
+            raise ValueError(f"calibration needs trials of both classes (got {int(rep['n_tgt'])} targets, "
+                             f"{int(rep['n_non'])} non-targets)")
+        if not rep["overflow"]:
+            break
+        cap = int(rep["blocks"])  # always the true number of blocks: the second call fits
+    nb = int(rep["blocks"])
+    return PavCalibration(*(x[:nb].cpu().numpy() for x in (lo, hi, llr, n, tt)), laplace=laplace, n_tgt=rep["n_tgt"],
+                          n_non=rep["n_non"], bins=rep["bins"])
+
+
 def calibrate_scorefile(dev_score_file, dev_key_file, score_file, method="gaussian", label_col=3, dev_skip_header=1,
                         skip_header=1, out=None, **fit_kw):
     """The reference's script body (:39-51): scores from the last column of `dev_score_file`, labels from column
     `label_col` of `dev_key_file` (row for row), a model trained on them, and `score_file` rewritten with its last column
     calibrated and formatted '{:f}'; every other byte of a data row and the header lines are kept.  The output path
     defaults to `score_file` with '_calibrated' in front of the extension.  method: "gaussian" (calibrate_train /
-    calibrate_apply) or "linear" (fit_linear, fit_kw = its keywords).  Returns (output path, model)."""
+    calibrate_apply), "linear" (fit_linear, fit_kw = its keywords) or "pav" (fit_pav, fit_kw = laplace).  Returns (output
+    path, model)."""
     from . import textio
-    if method not in ("gaussian", "linear"):
-        raise ValueError('method must be "gaussian" or "linear"')
+    if method not in ("gaussian", "linear", "pav"):
+        raise ValueError('method must be "gaussian", "linear" or "pav"')
 
     def body(path, skip):
         with open(path, "rb") as fh:
@@ -251,6 +306,8 @@ def calibrate_scorefile(dev_score_file, dev_key_file, score_file, method="gaussi
     labels = np.array(textio.column_tokens(key_text, label_col, n_key))
     if method == "gaussian":
         model = calibrate_train(dev_scores, labels)
+    elif method == "pav":
+        model = fit_pav(dev_scores, labels, **fit_kw)
     else:
         model = fit_linear(dev_scores, labels, **fit_kw)
     head, text = body(score_file, skip_header)

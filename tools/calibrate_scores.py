@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """Calibrate a score file: the command-line form of neuralplda_amd.score_calibration.calibrate_scorefile.
 
-    python tools/calibrate_scores.py DEV_SCORES DEV_KEY SCORES [--method gaussian|linear] [--out PATH]
+    python tools/calibrate_scores.py DEV_SCORES DEV_KEY SCORES [--method gaussian|linear|pav] [--out PATH]
                                      [--label-col 3] [--dev-skip-header 1] [--skip-header 1]
                                      [--p-target 0.5] [--l2 0] [--key EVAL_KEY] [--betas 99,199]
 
 Trains on the last column of DEV_SCORES with the labels of column --label-col of DEV_KEY ('target' / 'tgt',
 'nontarget' / 'imp'; other labels are ignored) and writes SCORES with its last column calibrated ('{:f}') to
 <SCORES>_calibrated<ext>.  With --key (a key file for SCORES, same layout as DEV_KEY) it also prints Cllr, the cost at
-the Bayes threshold (act_cost) and the minimum cost (minc_exact) before and after.  Needs a HIP device.
+the Bayes threshold (act_cost), the minimum cost (minc_exact) and min Cllr (the Cllr of the best monotone map, which
+calibration cannot change) before and after.  Needs a HIP device.
 """
 import argparse
 import os
@@ -34,7 +35,7 @@ def main(argv=None):
     ap.add_argument("dev_scores")
     ap.add_argument("dev_key")
     ap.add_argument("scores")
-    ap.add_argument("--method", choices=("gaussian", "linear"), default="gaussian")
+    ap.add_argument("--method", choices=("gaussian", "linear", "pav"), default="gaussian")
     ap.add_argument("--out", default=None)
     ap.add_argument("--label-col", type=int, default=3)
     ap.add_argument("--dev-skip-header", type=int, default=1)
@@ -61,7 +62,8 @@ def main(argv=None):
                 raise SystemExit(f"{path}: {s.numel()} scores but {target.numel()} key rows")
             act, _ = metrics.act_cost(s, target, betas)
             mc, _ = metrics.minc_exact(s.float(), target, betas)
-            print(f"{name:>6}: Cllr = {metrics.cllr(s, target):.6f}  act_cost = {act:.6f}  minc_exact = {float(mc):.6f}")
+            print(f"{name:>6}: Cllr = {metrics.cllr(s, target):.6f}  act_cost = {act:.6f}  minc_exact = {float(mc):.6f}  "
+                  f"min_Cllr = {metrics.min_cllr(s, target):.6f}")
 
 
 if __name__ == "__main__":
