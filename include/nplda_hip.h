@@ -237,6 +237,47 @@ int nplda_allpairs_loss_f32(const float* z, int64_t ldz, int64_t N, int D2, cons
                             float alpha, int kind, double* sums, float* loss, float* dtheta, float* dz, int64_t lddz,
                             float* dP_sqrt, float* dQ, void* ws, size_t ws_bytes, nplda_stream_t stream);
 
+/* ---- top-k search over an embedding table (csrc/nplda_topk.hip, design/k19_topk_search.md) ---------------------- */
+
+/* Largest k of nplda_topk_scores_f32. */
+#define NPLDA_TOPK_MAX_K 128
+
+/* Bytes of caller-provided workspace nplda_topk_scores_f32 needs for R rows against M table rows (k composites per row and
+ * column chunk of the table).  Never decreases with R, M or k.  0 for R outside 0 .. 2^24 - 1, M outside 0 .. 2^31 - 1, D2 above nplda_max_dim()
+ * or k outside 1 .. NPLDA_TOPK_MAX_K.  The number of chunks is chosen to fill the chip; the environment variable
+ * NPLDA_TOPK_MAX_CHUNKS, read at every call by this function and by nplda_topk_scores_f32 alike, can only lower its cap
+ * (fewer, longer chunks and less workspace; the result does not depend on it). */
+size_t nplda_topk_workspace_bytes(int64_t R, int64_t M, int D2, int k);
+
+/* 1:N search: for each of R probe rows the k best-scoring of the M rows of a table, with their indices — what the
+ * reference would do with forward_from_plda_embeddings (utils/models.py:372-376) on every pair, an R x M matrix and a sort;
+ * the matrix is never written here.  s_rj = q_rows[r] + q_tab[j] + 2 sum_d P_d z_rows[r, d] z_tab[j, d], P = P_sqrt^2 from
+ * `packed`; z_rows (R, ldz) / q_rows (R) and z_tab (M, ldz) / q_tab (M) come from nplda_embed_f32 (ldz >= nplda_padded_dim,
+ * ldz % 4 == 0; columns D2 .. ldz may hold any FINITE values, they meet P = 0; buffer rows beyond R and M are never read).
+ * Column j is ELIGIBLE for row r iff (grp_rows == NULL or grp_rows[r] == grp_tab[j]) and (self_rows == NULL or
+ * self_rows[r] != j) and (mask_mode 0: always; 1: lab_rows[r] != lab_tab[j]; 2: lab_rows[r] == lab_tab[j]) — by index and
+ * label only, never by value.  Labels and groups are int32 (lab_* may be NULL when mask_mode == 0; grp_rows / grp_tab are
+ * given both or neither); self_rows is int64 (R) or NULL: row r IS table row self_rows[r] (any value outside 0 .. M - 1
+ * excludes nothing).
+ * Output: vals (R, k) float and idx (R, k) int64, per row the k largest (largest = 1) or smallest (largest = 0) eligible
+ * scores, best first; equal fp32 scores (-0.0f counts as +0.0f) in ascending column order, inside the output and at the
+ * rank-k boundary: the result of a stable sort of the row.  A row with fewer than k eligible columns has idx = -1 and
+ * vals = -inf (largest) / +inf (smallest) in the remaining slots.  NaN scores are outside the ordering's contract.
+ * The fp32 value of s_rj depends on (row, column, model) only — fp32-input MFMAs, a fixed feature order — never on R, M,
+ * the chunking or the tile a column falls in, and so do vals and idx.  Two kernel launches on `stream` and nothing else (no
+ * allocation, no memset, no atomics, no synchronisation: capturable; bitwise repeatable).
+ * R == 0: a no-op.  M == 0: every slot is filled as for a short row.  NPLDA_EINVAL: a null required pointer, R or M < 0, k
+ * outside 1 .. NPLDA_TOPK_MAX_K, largest outside {0, 1}, mask_mode outside 0 .. 2 or labels missing for it, one of grp_rows /
+ * grp_tab without the other, z_rows / z_tab / packed / ws not 16-byte aligned, ldz not a multiple of 4 or below
+ * nplda_padded_dim(D1, D2); NPLDA_EUNSUPPORTED: a model outside the compiled kernel set, R above 2^24 - 1 (search more rows in
+ * several calls), M above 2^31 - 1;
+ * NPLDA_ENOSPC: ws_bytes below nplda_topk_workspace_bytes(R, M, D2, k). */
+int nplda_topk_scores_f32(const float* z_rows, const float* q_rows, int64_t R, const float* z_tab, const float* q_tab,
+                          int64_t M, int64_t ldz, const void* packed, int D0, int D1, int D2, int k, int largest,
+                          int mask_mode, const int32_t* lab_rows, const int32_t* lab_tab, const int32_t* grp_rows,
+                          const int32_t* grp_tab, const int64_t* self_rows, float* vals, int64_t* idx, void* ws,
+                          size_t ws_bytes, nplda_stream_t stream);
+
 /* ---- small resident-matrix GEMM on row batches (input gradients; csrc/nplda_matmul.hip) ---------------------- */
 
 /* MFMA-fragment image of a K x N matrix Wm (K <= 512, N % 4 == 0) for nplda_rows_matmul_f32.  mode 0: Wm = src (K, N)

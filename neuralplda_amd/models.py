@@ -553,6 +553,18 @@ class NeuralPlda(nn.Module):
         return _AllPairsLossFn.apply(z, speakers, groups, ops.LOSS_BCE, 0.0, [], opts, self.P_sqrt, self.Q,
                                      self.threshold_Xent)
 
+    def identify(self, x_probe, gallery_or_xvectors, k=10):
+        """1:N identification: (scores (R, k), indices (R, k)) of the k best-scoring gallery entries for every probe, best
+        first (-1 / -inf where the gallery has fewer than k).  The gallery is a search.Gallery (embedded once, reusable) or
+        the gallery's inputs, whatever extract_plda_embeddings takes; the probes x gallery matrix is never written."""
+        from . import search
+        g = gallery_or_xvectors
+        if not isinstance(g, search.Gallery):
+            g = search.Gallery.build(self, g)
+        elif g.model is not self:
+            raise ValueError("the Gallery was built with another model")
+        return g.search(x_probe, k=k)
+
     def cdet(self, output, target):
         """utils/models.py:401-404: hard detection cost at the model thresholds (strict < / >)."""
         dev = _compute_device(output, target)
@@ -677,6 +689,9 @@ class DPlda(NeuralPlda):
     def loss_all_pairs(self, x, speakers, groups=None):
         raise NotImplementedError("loss_all_pairs covers the NeuralPlda score (P_sqrt, Q); DPlda has a quadratic-form head")
 
+    def identify(self, x_probe, gallery_or_xvectors, k=10):
+        raise NotImplementedError("identify searches with the NeuralPlda score (P_sqrt, Q); DPlda has a quadratic-form head")
+
     def LoadParamsFromKaldi(self, mean_vec_file, transform_mat_file):
         """utils/models.py:551-564."""
         kaldi_format.fold_init(self, mean_vec_file, transform_mat_file)
@@ -750,6 +765,10 @@ class GaussianBackend(nn.Module):
         with torch.no_grad():
             s = ops.gb_score_pairs(_to_dev(x1, dev), _to_dev(x2, dev), W1, b1, *self._stats(dev))
         return s if s.device == x1.device else s.to(x1.device)
+
+    def identify(self, x_probe, gallery_or_xvectors, k=10):
+        raise NotImplementedError("identify searches with the NeuralPlda score (P_sqrt, Q); the Gaussian back end scores a "
+                                  "pair from its paired statistics")
 
     def forward_getpaired(self, x1, x2):
         """utils/models.py:595-601: [normalize(LDA x1), normalize(LDA x2)] -> (B, 2 D1)."""

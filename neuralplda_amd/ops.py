@@ -1144,6 +1144,65 @@ def cohort_stats(z_rows, q_rows, z_coh, q_coh, packed, topn=500, select="lowest"
     return stats
 
 
+TOPK_MAX_K = 128  # NPLDA_TOPK_MAX_K, include/nplda_hip.h
+_TOPK_MASKS = {None: 0, "different": 1, "same": 2}
+
+
+def topk_scores(z_rows, q_rows, z_tab, q_tab, packed, k, largest=True, labels=None, mask=None, groups=None, self_rows=None):
+    """nplda_topk_scores_f32: for each of the R rows the k best-scoring of the M table rows -> (vals (R, k) float32,
+    idx (R, k) int64), best first, equal scores in ascending column order; slots a row has no eligible column for hold
+    -1 and -inf (largest) / +inf (smallest).  The z tables and q vectors come from embed().  mask: None, "different" or "same"
+    with labels = (row labels (R,), table labels (M,)); groups = (row groups, table groups) restricts a row to the columns of
+    its group; self_rows (R,) int64 names the table row each row IS, which is then never returned for it.  The R x M score
+    matrix is never materialised."""
+    lib = _lib.load()
+    _need_fp32(packed, "topk_scores")
+    for n, t in (("z_rows", z_rows), ("q_rows", q_rows), ("z_tab", z_tab), ("q_tab", q_tab)):
+        _require_dev_f32(t, n)
+    for n, t in (("z_rows", z_rows), ("z_tab", z_tab)):
+        if t.dim() != 2 or t.shape[1] != packed.ldz or (t.shape[0] > 1 and t.stride(0) != packed.ldz) or t.stride(1) != 1:
+            raise ValueError(f"{n} must come from embed() (shape (rows, {packed.ldz}), row stride = packed.ldz)")
+    R, M, dev = z_rows.shape[0], z_tab.shape[0], z_rows.device
+    if q_rows.shape != (R,) or q_tab.shape != (M,):
+        raise ValueError("q_rows / q_tab must hold one self term per row of z_rows / z_tab")
+    if z_tab.device != dev or packed.device != dev:
+        raise ValueError("z_rows, z_tab and the packed model must live on one device")
+    k = int(k)
+    if not 1 <= k <= TOPK_MAX_K:
+        raise ValueError(f"k must be in 1 .. {TOPK_MAX_K} (got {k})")
+    if mask not in _TOPK_MASKS:
+        raise ValueError("mask must be None, 'different' or 'same'")
+    lab_r = lab_t = grp_r = grp_t = None
+    if mask is not None:
+        if labels is None or len(labels) != 2:
+            raise ValueError("mask needs labels = (row labels, table labels)")
+        lab_r, lab_t = _labels(labels[0], "labels[0]", R, dev), _labels(labels[1], "labels[1]", M, dev)
+    if groups is not None:
+        if len(groups) != 2:
+            raise ValueError("groups = (row groups, table groups)")
+        grp_r, grp_t = _labels(groups[0], "groups[0]", R, dev), _labels(groups[1], "groups[1]", M, dev)
+    if self_rows is not None:
+        self_rows = _idx(self_rows, "self_rows", dev)
+        if self_rows.shape != (R,):
+            raise ValueError("self_rows must name one table row per row of z_rows")
+    vals = torch.empty((R, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((R, k), dtype=torch.int64, device=dev)
+    if R == 0:
+        return vals, idx
+    wsb = lib.nplda_topk_workspace_bytes(R, M, packed.D2, k)
+    if wsb == 0:
+        raise _lib.NpldaHipError(f"topk_scores: R = {R}, M = {M}, D2 = {packed.D2}, k = {k} is outside the compiled kernel set")
+    ws = torch.empty(wsb // 4, dtype=torch.float32, device=dev)
+    with _lib.on_device(dev):
+        code = lib.nplda_topk_scores_f32(_lib.ptr(z_rows), _lib.ptr(q_rows.contiguous()), R, _lib.ptr(z_tab),
+                                         _lib.ptr(q_tab.contiguous()), M, packed.ldz, _lib.ptr(packed.buf), packed.D0, packed.D1,
+                                         packed.D2, k, 1 if largest else 0, _TOPK_MASKS[mask], _lib.ptr(lab_r), _lib.ptr(lab_t),
+                                         _lib.ptr(grp_r), _lib.ptr(grp_t), _lib.ptr(self_rows), _lib.ptr(vals), _lib.ptr(idx),
+                                         _lib.ptr(ws), wsb, _lib.current_stream())
+    _lib.check(code, "nplda_topk_scores_f32")
+    return vals, idx
+
+
 def row_stats(S, topn=500, select="lowest"):
     """nplda_row_stats_f32 on an explicit (R, M) float32 score matrix."""
     lib = _lib.load()

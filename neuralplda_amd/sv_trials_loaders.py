@@ -634,3 +634,74 @@ class SpeakerBatchLoader:
                 spk = torch.from_numpy(spk).to(self.device)
                 grp = None if grp is None else torch.from_numpy(grp).to(self.device)
             yield rows, spk, grp
+
+
+# ---------------------------------------------------------------------------------------------------
+# hard trials mined from a table: the producer of (rows1, rows2, target) lists for index training
+# ---------------------------------------------------------------------------------------------------
+
+def canonical_trials(rows, neg_idx=None, pos_idx=None):
+    """Search results -> one trial list.  rows (U,) int64: the table row of each searched utterance; neg_idx (U, kn) and
+    pos_idx (U, kp) int64: per utterance the POSITIONS (into `rows`) of its mined non-targets / targets, -1 for an unused slot.
+    Returns (rows1, rows2, target float32) in table-row numbering: unordered pairs made canonical (rows1 < rows2), each kept
+    once however many times and from whichever side it was found, sorted by (rows1, rows2).  Pure tensor code: runs on CPU
+    tensors as on device tensors."""
+    rows = torch.as_tensor(rows)
+    keys = []
+    span = int(rows.max().item()) + 1 if rows.numel() else 1
+    for idx, tgt in ((neg_idx, 0), (pos_idx, 1)):
+        if idx is None or idx.numel() == 0:
+            continue
+        keep = idx >= 0
+        a = rows[:, None].expand_as(idx)[keep]
+        b = rows[idx[keep]]
+        lo, hi = torch.minimum(a, b), torch.maximum(a, b)
+        ok = lo != hi
+        keys.append(((lo[ok] * span + hi[ok]) * 2 + tgt))
+    if not keys:
+        e = torch.empty(0, dtype=torch.int64, device=rows.device)
+        return e, e.clone(), torch.empty(0, dtype=torch.float32, device=rows.device)
+    key = torch.unique(torch.cat(keys))  # sorted
+    pair = key // 2
+    return pair // span, pair % span, (key % 2).to(torch.float32)
+
+
+def mine_hard_trials(model, table, spk2utt, negatives_per_utt, positives_per_utt=0, groups=None, device=None, chunk_rows=None):
+    """Hard trials of a training table for index training (TrialIndexDataset / ops.train_step_rows): every utterance of
+    `spk2utt` that the table holds is embedded once, and the table is searched against itself (ops.topk_scores) for each
+    utterance's `negatives_per_utt` HIGHEST-scoring utterances of other speakers and, optionally, its `positives_per_utt`
+    LOWEST-scoring utterances of its own speaker (itself excluded) — inside its group when `groups` is given (as
+    SpeakerBatchLoader takes it).  Returns device tensors (rows1 int64, rows2 int64, target float32), table-row numbering,
+    canonical and deduplicated (canonical_trials).  chunk_rows: utterances searched per call (default 16 384)."""
+    from . import ops, search
+    from .adaptive_score_normalization import _model_params
+    kn, kp = int(negatives_per_utt), int(positives_per_utt)
+    if kn < 0 or kp < 0 or kn + kp == 0:
+        raise ValueError("negatives_per_utt and positives_per_utt must be non-negative and not both zero")
+    ld = SpeakerBatchLoader(table, spk2utt, 1, 1, groups=groups)  # (its reading of spk2utt and groups; no batch is drawn)
+    rows = np.concatenate(ld._rows) if ld._rows else np.zeros(0, np.int64)
+    spk = np.concatenate([np.full(r.size, s, np.int32) for s, r in enumerate(ld._rows)]) if ld._rows else np.zeros(0, np.int32)
+    rows, first = np.unique(rows, return_index=True)  # ascending table rows; an utterance listed twice keeps its first speaker
+    spk = spk[first]
+    grp = None if ld._group is None else ld._group[spk]
+    dev = search._search_device(model, None) if device is None else torch.device(device)
+    rows_d = torch.from_numpy(rows).to(dev)
+    U = rows.size
+    if U == 0:
+        return canonical_trials(rows_d)
+    with torch.no_grad():
+        packed = ops.pack_params(*_model_params(model, dev))
+        z, q = search.embed_table(model, ops.gather_rows(table.on(dev), rows_d), packed)
+        spk_d = torch.from_numpy(spk).to(dev)
+        grp_d = None if grp is None else torch.from_numpy(grp).to(dev)
+        step = int(chunk_rows) if chunk_rows else 16384
+        me = torch.arange(U, dtype=torch.int64, device=dev)
+        neg, pos = [], []
+        for lo in range(0, U, step):
+            hi = min(U, lo + step)
+            kw = dict(labels=(spk_d[lo:hi], spk_d), groups=None if grp_d is None else (grp_d[lo:hi], grp_d), self_rows=me[lo:hi])
+            if kn:
+                neg.append(ops.topk_scores(z[lo:hi], q[lo:hi], z, q, packed, kn, largest=True, mask="different", **kw)[1])
+            if kp:
+                pos.append(ops.topk_scores(z[lo:hi], q[lo:hi], z, q, packed, kp, largest=False, mask="same", **kw)[1])
+    return canonical_trials(rows_d, torch.cat(neg) if neg else None, torch.cat(pos) if pos else None)
