@@ -27,7 +27,6 @@
 #include <cstring>
 #include "nplda_train_fb_small.h"
 #include "nplda_train_fb_half.h"
-#include <cstdlib>
 #include "nplda_wgrad_fm.h"
 
 namespace nplda {  // nplda_matmul.hip
@@ -798,6 +797,23 @@ static inline bool wgrad_fm_bf16_ok(long long B, long long ldx, const NpldaLayou
            (L.D0 % 2) == 0;
 }
 
+// The shape of one "A^T B" problem: all Mp padded columns of A against N columns of B, slab rows of Np floats; the 64 x 64
+// tile counts follow.  The caller names the operands (A, lda, B0, B1, ldb, slab).
+static WgradProblem wgrad_problem(int Mp, int N, int Np, int extras) {
+    WgradProblem p = {};
+    p.M = p.Mp = Mp; p.N = N; p.Np = Np; p.extras = extras;
+    p.MT = (Mp + 63) / 64; p.NT = (N + 63) / 64;
+    return p;
+}
+
+// The work items of `nprob` problems (1 or 2): their tiles per k-group, then (pair_sums) one pair-sum block per k-group.
+static void wgrad_count(WgradArgs& wa, int nprob, bool pair_sums) {
+    if (nprob < 2) wa.p[1] = wa.p[0];  // never scheduled (nw_mm == nw0)
+    wa.nw0 = wa.p[0].MT * wa.p[0].NT * wa.ksplit;
+    wa.nw_mm = nprob < 2 ? wa.nw0 : wa.nw0 + wa.p[1].MT * wa.p[1].NT * wa.ksplit;
+    wa.nw = wa.nw_ps = wa.nw_mm + (pair_sums ? wa.ksplit : 0);
+}
+
 // The weight-gradient launch: full-M form where it applies, the 64 x 64 form otherwise.  nprob: problems in use (1 or 2).
 // tail: the training step's loss tail, to ride along if the full-M form runs (*tail_done reports it).
 static int wgrad_launch(WgradArgs& wa, int NB, int nprob, hipStream_t st, const LossTail* tail = nullptr,
@@ -925,6 +941,7 @@ __device__ __forceinline__ size_t frag_pos(int f, int k, int NB) {
     return ((((size_t)(k >> 4) * NB + (f >> 4)) * 64 + (((k & 15) >> 2) << 4) + (f & 15)) << 2) + (k & 3);
 }
 
+constexpr int kUpdateE = 2;  // both launches; without arrival tickets (the first kernel has counted the step) small blocks are free
 template <int E>  // elements per thread
 __global__ __launch_bounds__(256) void train_update_kernel(const UpdateArgs a) {
     const float t = a.bumped ? a.step[0] : a.step[0] + 1.0f;
@@ -1052,6 +1069,12 @@ __global__ __launch_bounds__(256) void train_update_kernel(const UpdateArgs a) {
     }
 }
 
+static int launch_update(const UpdateArgs& ua, hipStream_t st) {
+    const dim3 grid(ua.ngrad_blocks + (unsigned)ua.tail_here + ua.ncopy);
+    hipLaunchKernelGGL(train_update_kernel<kUpdateE>, grid, dim3(256), 0, st, ua);
+    return nplda_launch_status();
+}
+
 // ------------------------------------------------------------------------------------------------
 constexpr int kBwdWaves = 4;
 
@@ -1064,11 +1087,7 @@ struct WsLayout {
 
 // persistent grid of bwd_data_stream_kernel: one 8-wave block per CU (each wave walks 16-pair tiles)
 static inline long long stream_grid(long long nA) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        cus = 256;
-    const long long need = (nA + 127) / 128;
+    const long long need = (nA + 127) / 128, cus = mid_cus();
     return need < cus ? (need > 0 ? need : 1) : cus;
 }
 
@@ -1111,50 +1130,63 @@ WsLayout ws_layout(long long K, const NpldaLayout& L, bool want_dx) {
     return w;
 }
 
+// What backward_launch is asked for: a plain host struct, filled by member name.
+struct BwdRequest {
+    // given == false: pair scoring — dz is formed from g, z (rows [0,B) = x1 side, [B,2B) = x2 side);
+    // given == true : `K` embedding rows whose upstream gradient dL/dz already sits, zero-padded, in the workspace.
+    bool given;
+    const float* xa; const float* xb; long long K, nsplit, ldx; bool x_bf16;          // the rows
+    const float* g; const float* y; const float* z; const float* rn; long long ldz;   // the saved activations
+    const float* packed; NpldaLayout L; const float* P_sqrt; float* wsf; WsLayout W;  // the model, the workspace
+    float* grad_flat; float* dx0; float* dx1; long long lddx;                         // the outputs
+    hipStream_t st;
+    struct {                       // the fused training step's part (train_step_impl only)
+        const BwdLoss* ls;         // the loss the first kernel folded in: the weight gradients take g from ls->g_out
+        ReduceArgs* defer_reduce;  // gets K-C's arguments instead of a launch: the caller's update kernel sums the slabs
+        bool data_done;            // train_fb_small_kernel has already left dz, du, the pair sums and the loss partials
+        const LossTail* tail;      // the loss tail, to ride in the weight-gradient launch if its full-M form runs,
+        bool* tail_done;           //   which this reports
+        int pq_rows = -1;          // rows of pair sums the first kernel left when not one per 16-pair tile (the half-tile kernels)
+    } fused;
+};
+
 // The three launches (+ the input-gradient GEMM when dx is asked for) behind every backward entry point.
-//   given == false: pair scoring — dz is formed from g, z (rows [0,B) = x1 side, [B,2B) = x2 side);
-//   given == true : `K` embedding rows whose upstream gradient dL/dz already sits, zero-padded, in the workspace.
-int backward_launch(bool given, const float* xa, const float* xb, long long K, long long nsplit, long long ldx,
-                    const float* packed, const NpldaLayout& L, const float* g, const float* y, const float* z,
-                    const float* rn, long long ldz, const float* P_sqrt, float* wsf, const WsLayout& W, float* grad_flat,
-                    float* dx0, float* dx1, long long lddx, hipStream_t st, const BwdLoss* ls = nullptr,
-                    ReduceArgs* defer_reduce = nullptr, bool data_done = false, const LossTail* tail = nullptr,
-                    bool* tail_done = nullptr, bool x_bf16 = false, int pq_rows = -1) {
+int backward_launch(const BwdRequest& q) {
     BwdArgs b = {};
-    if (ls) {
-        if (given || nsplit > 16 * 1024) return NPLDA_EUNSUPPORTED;
-        b.ls = *ls;
+    if (q.fused.ls) {
+        if (q.given || q.nsplit > 16 * 1024) return NPLDA_EUNSUPPORTED;
+        b.ls = *q.fused.ls;
     }
-    b.g = g; b.z = z; b.y = y; b.rn = rn; b.packed = packed; b.ldz = ldz;
-    if (given) {
-        b.nA = (K + 1) / 2; b.nB = K - b.nA; b.offB = b.nB > 0 ? b.nA : 0;
+    b.g = q.g; b.z = q.z; b.y = q.y; b.rn = q.rn; b.packed = q.packed; b.ldz = q.ldz;
+    if (q.given) {
+        b.nA = (q.K + 1) / 2; b.nB = q.K - b.nA; b.offB = b.nB > 0 ? b.nA : 0;
     } else {
-        b.nA = b.nB = b.offB = nsplit;
+        b.nA = b.nB = b.offB = q.nsplit;
     }
-    b.oW2T = L.oW2T; b.oQ = L.oQ; b.oP = L.oP; b.total = L.total;
-    b.dz = wsf + W.dz; b.du = wsf + W.du;
+    b.oW2T = q.L.oW2T; b.oQ = q.L.oQ; b.oP = q.L.oP; b.total = q.L.total;
+    b.dz = q.wsf + q.W.dz; b.du = q.wsf + q.W.du;
     // K-A leaves the dQ / dP pair sums per block: the small-batch kernel one row per 16-pair tile, the streaming kernel
     // (NB >= 8) one row per persistent block
     const long long stream_blocks = stream_grid(b.nA);
-    const bool pair_sums = !given && (b.nA <= 16 * 1024 || L.NB >= 8);
-    b.pq = pair_sums ? wsf + W.pq : nullptr;
+    const bool pair_sums = !q.given && (b.nA <= 16 * 1024 || q.L.NB >= 8);
+    b.pq = pair_sums ? q.wsf + q.W.pq : nullptr;
     const long long ntb = (b.nA + 16 * kBwdWaves - 1) / (16 * kBwdWaves);
     if (ntb > 0x7fffffffLL) return NPLDA_EINVAL;
     b.ntb = (int)ntb;
-    if (!data_done) {  // (data_done: train_fb_small_kernel has already left dz, du, the pair sums and the loss partials)
+    if (!q.fused.data_done) {
         // small batches: 4 waves share a 16-pair tile (feature split), so a 4096-pair minibatch fills 256 CUs
         const bool small = b.nA <= 16 * 1024;
-        const bool stream = !small && L.NB >= 8;
+        const bool stream = !small && q.L.NB >= 8;
         dim3 grid(small ? (unsigned)((b.nA + 15) / 16) : (stream ? (unsigned)stream_blocks : (unsigned)(ntb < 2048 ? ntb : 2048))),
             block(stream ? 512 : 256);
 #define NPLDA_LAUNCH2(NBV, GV)                                                                  \
-    if (small) hipLaunchKernelGGL((bwd_data_small_kernel<NBV, GV>), grid, block, 0, st, b);      \
-    else if (NBV >= 8) hipLaunchKernelGGL((bwd_data_stream_kernel<(NBV >= 8 ? NBV : 8), GV>), grid, block, 0, st, b);   \
-    else hipLaunchKernelGGL((bwd_data_kernel<NBV, kBwdWaves, GV>), grid, block, 0, st, b)
+    if (small) hipLaunchKernelGGL((bwd_data_small_kernel<NBV, GV>), grid, block, 0, q.st, b);    \
+    else if (NBV >= 8) hipLaunchKernelGGL((bwd_data_stream_kernel<(NBV >= 8 ? NBV : 8), GV>), grid, block, 0, q.st, b); \
+    else hipLaunchKernelGGL((bwd_data_kernel<NBV, kBwdWaves, GV>), grid, block, 0, q.st, b)
 #define NPLDA_LAUNCH(NBV)                                                                        \
-    if (ls) hipLaunchKernelGGL((bwd_data_small_kernel<NBV, false, true>), grid, block, 0, st, b); \
-    else if (given) { NPLDA_LAUNCH2(NBV, true); } else { NPLDA_LAUNCH2(NBV, false); }
-        switch (L.NB) {
+    if (q.fused.ls) hipLaunchKernelGGL((bwd_data_small_kernel<NBV, false, true>), grid, block, 0, q.st, b); \
+    else if (q.given) { NPLDA_LAUNCH2(NBV, true); } else { NPLDA_LAUNCH2(NBV, false); }
+        switch (q.L.NB) {
             case 2: NPLDA_LAUNCH(2); break;
             case 4: NPLDA_LAUNCH(4); break;
             case 8: NPLDA_LAUNCH(8); break;
@@ -1169,37 +1201,33 @@ int backward_launch(bool given, const float* xa, const float* xb, long long K, l
     }
     // K-B
     WgradArgs wa = {};
-    wa.K = K; wa.nsplit = nsplit; wa.ksplit = W.ksplit; wa.rows_per_split = W.rows_per_split;
-    wa.z = z; wa.g = ls ? ls->g_out : g; wa.ldz = ldz; wa.ext = wsf + W.ext; wa.Mp = W.Mp;
-    WgradProblem& p1 = wa.p[0];  // dW1 = du^T [x1; x2]
-    p1.A = wsf + W.du; p1.lda = ldz; p1.B0 = xa; p1.B1 = xb; p1.ldb = ldx; p1.M = W.Mp; p1.N = L.D0;
-    p1.MT = (W.Mp + 63) / 64; p1.NT = (L.D0 + 63) / 64; p1.slab = wsf + W.slab1; p1.Mp = W.Mp; p1.Np = W.Np1; p1.extras = 1;
-    p1.b_bf16 = x_bf16 ? 1 : 0;  // (xa / xb then point at bfloat16 rows, ldx counts elements)
-    WgradProblem& p2 = wa.p[1];  // dW2 = dz^T [y1; y2]
-    p2.A = wsf + W.dz; p2.lda = ldz; p2.B0 = y; p2.B1 = y + (size_t)nsplit * ldz; p2.ldb = ldz; p2.M = W.Mp; p2.N = W.Mp;
-    p2.MT = (W.Mp + 63) / 64; p2.NT = (W.Mp + 63) / 64; p2.slab = wsf + W.slab2; p2.Mp = W.Mp; p2.Np = W.Mp;
-    p2.extras = given ? 3 : (pair_sums ? 4 : 2);
-    wa.nw0 = p1.MT * p1.NT * W.ksplit;
-    wa.nw_mm = wa.nw0 + p2.MT * p2.NT * W.ksplit;
-    wa.nw = wa.nw_ps = wa.nw_mm + (pair_sums ? W.ksplit : 0);
-    // (pq_rows: rows of pair sums the data kernel left when it was not one per 16-pair tile — the half-tile kernels)
-    wa.pq = b.pq; wa.nblk = pq_rows >= 0 ? pq_rows : (b.nA <= 16 * 1024 ? (int)((b.nA + 15) / 16) : (int)stream_blocks);
-    if (int rc = wgrad_launch(wa, L.NB, 2, st, tail, tail_done)) return rc;
+    wa.K = q.K; wa.nsplit = q.nsplit; wa.ksplit = q.W.ksplit; wa.rows_per_split = q.W.rows_per_split;
+    wa.z = q.z; wa.g = q.fused.ls ? q.fused.ls->g_out : q.g; wa.ldz = q.ldz; wa.ext = q.wsf + q.W.ext; wa.Mp = q.W.Mp;
+    WgradProblem& p1 = wa.p[0] = wgrad_problem(q.W.Mp, q.L.D0, q.W.Np1, 1);  // dW1 = du^T [x1; x2]
+    p1.A = q.wsf + q.W.du; p1.lda = q.ldz; p1.B0 = q.xa; p1.B1 = q.xb; p1.ldb = q.ldx; p1.slab = q.wsf + q.W.slab1;
+    p1.b_bf16 = q.x_bf16 ? 1 : 0;  // (xa / xb then point at bfloat16 rows, ldx counts elements)
+    WgradProblem& p2 = wa.p[1] = wgrad_problem(q.W.Mp, q.W.Mp, q.W.Mp, q.given ? 3 : (pair_sums ? 4 : 2));  // dW2 = dz^T [y1; y2]
+    p2.A = q.wsf + q.W.dz; p2.lda = p2.ldb = q.ldz; p2.B0 = q.y; p2.B1 = q.y + (size_t)q.nsplit * q.ldz;
+    p2.slab = q.wsf + q.W.slab2;
+    wgrad_count(wa, 2, pair_sums);
+    wa.pq = b.pq;
+    wa.nblk = q.fused.pq_rows >= 0 ? q.fused.pq_rows : (b.nA <= 16 * 1024 ? (int)((b.nA + 15) / 16) : (int)stream_blocks);
+    if (int rc = wgrad_launch(wa, q.L.NB, 2, q.st, q.fused.tail, q.fused.tail_done)) return rc;
     // K-C
     ReduceArgs ra = {};
-    ra.slab1 = wsf + W.slab1; ra.slab2 = wsf + W.slab2; ra.ext = wsf + W.ext; ra.P_sqrt = P_sqrt;
-    ra.ksplit = W.ksplit; ra.Mp = W.Mp; ra.Np1 = W.Np1; ra.D0 = L.D0; ra.D1 = L.D1; ra.D2 = L.D2; ra.out = grad_flat;
-    const size_t ngrad = (size_t)L.D1 * L.D0 + L.D1 + (size_t)L.D2 * L.D1 + 3 * (size_t)L.D2;
-    if (defer_reduce) {  // the caller's update kernel sums the slabs itself
-        *defer_reduce = ra;
+    ra.slab1 = q.wsf + q.W.slab1; ra.slab2 = q.wsf + q.W.slab2; ra.ext = q.wsf + q.W.ext; ra.P_sqrt = q.P_sqrt;
+    ra.ksplit = q.W.ksplit; ra.Mp = q.W.Mp; ra.Np1 = q.W.Np1; ra.D0 = q.L.D0; ra.D1 = q.L.D1; ra.D2 = q.L.D2; ra.out = q.grad_flat;
+    if (q.fused.defer_reduce) {  // the caller's update kernel sums the slabs itself
+        *q.fused.defer_reduce = ra;
         return NPLDA_OK;
     }
-    hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)((ngrad + 255) / 256)), dim3(256), 0, st, ra);
+    const size_t ngrad = nplda_grad_floats(q.L.D0, q.L.D1, q.L.D2);
+    hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)((ngrad + 255) / 256)), dim3(256), 0, q.st, ra);
     if (int rc = nplda_launch_status()) return rc;
-    if (dx0) {  // dL/dx = du . W1 (the E2E head's input gradient, utils/models.py:251-268)
-        return input_grad_from_du(wsf + W.du, K, ldz, packed, L, wsf + W.frag, dx0, dx1, nsplit, lddx, st);
-    }
-    return NPLDA_OK;
+    if (!q.dx0) return NPLDA_OK;
+    // dL/dx = du . W1 (the E2E head's input gradient, utils/models.py:251-268)
+    return input_grad_from_du(q.wsf + q.W.du, q.K, q.ldz, q.packed, q.L, q.wsf + q.W.frag, q.dx0, q.dx1, q.nsplit, q.lddx,
+                              q.st);
 }
 
 }  // namespace
@@ -1217,12 +1245,9 @@ int gram_slabs_launch(const float* Z, long long ldz, long long rows, int Mp, int
     WgradArgs wa = {};
     wa.K = rows; wa.nsplit = rows; wa.ksplit = ksplit; wa.rows_per_split = rps;
     wa.ldz = ldz; wa.ext = ext; wa.Mp = Mp;
-    WgradProblem& p1 = wa.p[0];
-    p1.A = Z; p1.lda = ldz; p1.B0 = Z; p1.B1 = Z; p1.ldb = ldz; p1.M = Mp; p1.N = Mp;
-    p1.MT = (Mp + 63) / 64; p1.NT = (Mp + 63) / 64; p1.slab = slab; p1.Mp = Mp; p1.Np = Mp; p1.extras = 1;
-    wa.p[1] = p1;
-    wa.nw0 = p1.MT * p1.NT * ksplit;
-    wa.nw = wa.nw_mm = wa.nw_ps = wa.nw0;
+    WgradProblem& p1 = wa.p[0] = wgrad_problem(Mp, Mp, Mp, 1);
+    p1.A = Z; p1.lda = ldz; p1.B0 = Z; p1.B1 = Z; p1.ldb = ldz; p1.slab = slab;
+    wgrad_count(wa, 1, false);
     if (qz) {
         wa.qz = *qz;
         wa.nw += qz->nblocks;
@@ -1232,6 +1257,12 @@ int gram_slabs_launch(const float* Z, long long ldz, long long rows, int Mp, int
 }
 
 }  // namespace nplda
+
+// an empty batch: its gradient
+static int zero_gradient(float* p, size_t n, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(p, 0, n * sizeof(float), st);
+    return e == hipSuccess ? NPLDA_OK : (int)e;
+}
 
 extern "C" {
 
@@ -1288,28 +1319,27 @@ int nplda_backward_ex_f32(const float* x1, const float* x2, int64_t B, int64_t l
     if (int rc = check_model(D0, D1, D2)) return rc;
     if (!grad_flat) return NPLDA_EINVAL;
     if ((dx1 == nullptr) != (dx2 == nullptr)) return NPLDA_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const NpldaLayout L = nplda_layout(D0, D1, D2);
-    const size_t ngrad = nplda_grad_floats(D0, D1, D2);
-    if (B == 0) {
-        hipError_t e = hipMemsetAsync(grad_flat, 0, ngrad * sizeof(float), st);
-        return e == hipSuccess ? NPLDA_OK : (int)e;
-    }
+    BwdRequest q = {};
+    q.st = (hipStream_t)stream;
+    q.L = nplda_layout(D0, D1, D2);
+    if (B == 0) return zero_gradient(grad_flat, nplda_grad_floats(D0, D1, D2), q.st);
     if (!packed || !g || !rn || !P_sqrt || !ws || !nplda_aligned16(packed) || !nplda_aligned16(ws)) return NPLDA_EINVAL;
     if (!rows_ok(x1, ldx, D0) || !rows_ok(x2, ldx, D0)) return NPLDA_EINVAL;
-    if (!rows_ok(y, ldz, 16 * L.NB) || !rows_ok(z, ldz, 16 * L.NB) || ldz != 16 * L.NB) return NPLDA_EINVAL;
+    if (!rows_ok(y, ldz, 16 * q.L.NB) || !rows_ok(z, ldz, 16 * q.L.NB) || ldz != 16 * q.L.NB) return NPLDA_EINVAL;
     if (dx1 && (!rows_ok(dx1, lddx, D0) || !rows_ok(dx2, lddx, D0))) return NPLDA_EINVAL;
-    const WsLayout W = ws_layout(2 * B, L, dx1 != nullptr);
-    if (ws_bytes < W.total * sizeof(float)) return NPLDA_ENOSPC;
-    return backward_launch(false, x1, x2, 2 * B, B, ldx, (const float*)packed, L, g, y, z, rn, ldz, P_sqrt, (float*)ws, W,
-                           grad_flat, dx1, dx2, lddx, st);
+    q.W = ws_layout(2 * B, q.L, dx1 != nullptr);
+    if (ws_bytes < q.W.total * sizeof(float)) return NPLDA_ENOSPC;
+    q.xa = x1; q.xb = x2; q.K = 2 * B; q.nsplit = B; q.ldx = ldx; q.g = g; q.y = y; q.z = z; q.rn = rn; q.ldz = ldz;
+    q.packed = (const float*)packed; q.P_sqrt = P_sqrt; q.wsf = (float*)ws;
+    q.grad_flat = grad_flat; q.dx0 = dx1; q.dx1 = dx2; q.lddx = lddx;
+    return backward_launch(q);
 }
 
 int nplda_backward_f32(const float* x1, const float* x2, int64_t B, int64_t ldx, const void* packed, int D0, int D1,
                        int D2, const float* g, const float* y, const float* z, const float* rn, int64_t ldz,
                        const float* P_sqrt, void* ws, size_t ws_bytes, float* grad_flat, nplda_stream_t stream) {
     return nplda_backward_ex_f32(x1, x2, B, ldx, packed, D0, D1, D2, g, y, z, rn, ldz, P_sqrt, ws, ws_bytes, grad_flat,
-                                 nullptr, nullptr, 0, stream);
+                                 /*dx1*/ nullptr, /*dx2*/ nullptr, /*lddx*/ 0, stream);  // (the one ABI in terms of the other)
 }
 
 int nplda_embed_backward_f32(const float* x, int64_t N, int64_t ldx, const void* packed, int D0, int D1, int D2,
@@ -1320,20 +1350,18 @@ int nplda_embed_backward_f32(const float* x, int64_t N, int64_t ldx, const void*
     if (!grad_flat) return NPLDA_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const NpldaLayout L = nplda_layout(D0, D1, D2);
-    const size_t ngrad = nplda_grad_floats(D0, D1, D2);
-    if (N == 0) {
-        hipError_t e = hipMemsetAsync(grad_flat, 0, ngrad * sizeof(float), st);
-        return e == hipSuccess ? NPLDA_OK : (int)e;
-    }
+    if (N == 0) return zero_gradient(grad_flat, nplda_grad_floats(D0, D1, D2), st);
     if (!packed || !gz || !rn || !ws || ldgz < D2 || !nplda_aligned16(packed) || !nplda_aligned16(ws)) return NPLDA_EINVAL;
     if (!rows_ok(x, ldx, D0) || !rows_ok(y, ldz, 16 * L.NB) || ldz != 16 * L.NB) return NPLDA_EINVAL;
     if (dx && !rows_ok(dx, lddx, D0)) return NPLDA_EINVAL;
-    const WsLayout W = ws_layout(N, L, dx != nullptr);
-    if (ws_bytes < W.total * sizeof(float)) return NPLDA_ENOSPC;
-    float* wsf = (float*)ws;
-    if (int rc = pad_rows(gz, ldgz, N, D2, wsf + W.dz, ldz, st)) return rc;
-    return backward_launch(true, x, x, N, N, ldx, (const float*)packed, L, nullptr, y, nullptr, rn, ldz, nullptr, wsf, W,
-                           grad_flat, dx, dx, lddx, st);
+    BwdRequest q = {};
+    q.given = true;  // (no g, z, P_sqrt: dL/dz is given, dP = dQ = 0)
+    q.xa = x; q.xb = x; q.K = N; q.nsplit = N; q.ldx = ldx; q.y = y; q.rn = rn; q.ldz = ldz;
+    q.packed = (const float*)packed; q.L = L; q.wsf = (float*)ws; q.W = ws_layout(N, L, dx != nullptr);
+    q.grad_flat = grad_flat; q.dx0 = dx; q.dx1 = dx; q.lddx = lddx; q.st = st;
+    if (ws_bytes < q.W.total * sizeof(float)) return NPLDA_ENOSPC;
+    if (int rc = pad_rows(gz, ldgz, N, D2, q.wsf + q.W.dz, ldz, st)) return rc;
+    return backward_launch(q);
 }
 
 // ---- the fused training step --------------------------------------------------------------------------------
@@ -1379,6 +1407,78 @@ static StepWs step_ws(long long B, const NpldaLayout& L, bool rows) {
     w.total = w.bwd + ws_layout(2 * B, L, false).total;
     return w;
 }
+
+// What a training entry point asks for: a plain host struct of groups, filled group by group and never passed to a kernel.
+struct TrainStep {
+    // the batch: direct rows x1 / x2; or a table (x1 == x2) with `ntab` rows and the indices rows1 / rows2; or (cursor) the
+    // staged record [rows1 | rows2 | labels] of a device-resident epoch.  io_bf16: x1 / x2 and dx are bfloat16 rows.
+    // loss.gcount: the global batch's counts (the data-parallel gradient phase).
+    struct Batch {
+        const float* x1; const float* x2; int64_t B, ldx; const float* target;
+        const int64_t* rows1; const int64_t* rows2; int64_t ntab; long long* cursor; void* stage; bool io_bf16;
+    } in;
+    struct Model { float* const* params; int D0, D1, D2; void* packed; void* ws; size_t ws_bytes; } net;
+    struct Loss { float* const* thetas; const float* betas; int K; float alpha; int kind; const double* gcount; } loss;
+    struct Optim { float* exp_avg; float* exp_avg_sq; float* step; float lr, beta1, beta2, eps, wd; } opt;
+    struct Outputs { float* loss; double* loss_sum; float* grad_out; void* dxa; void* dxb; int64_t lddx; } out;
+    // the mode.  grad_only: the data-parallel gradient phase — the same three launches, but the last two stop at this rank's flat
+    // gradient flat = [ngrad | loss sums as kLossLimbs x kLossNS floats] and nothing is updated: of the optimiser only `step` is
+    // asked for (the first kernel counts the step), of the outputs only the dx rows.
+    bool grad_only; float* flat;
+    nplda_stream_t stream;
+};
+
+// The gradient phase's request but for its batch, dx rows and stream: no moments, hyper-parameters or loss address (fill_update)
+static TrainStep grad_step(const TrainStep::Model& net, const TrainStep::Loss& loss, float* step, float* flat) {
+    TrainStep t = {};
+    t.net = net; t.loss = loss; t.opt.step = step; t.grad_only = true; t.flat = flat;
+    return t;
+}
+
+// kind / K / thetas / betas / params, as the step and nplda_train_step_apply_f32 check them.  *nth: thresholds in use.
+static int check_loss_spec(const TrainStep& t, int* nth) {
+    if (t.loss.kind != 0 && t.loss.kind != 1) return t.loss.kind == 2 ? NPLDA_EUNSUPPORTED : NPLDA_EINVAL;
+    *nth = t.loss.kind == 1 ? 1 : t.loss.K;
+    if (*nth < 1 || *nth > nplda_loss::kMaxK || !t.loss.thetas || !t.net.params || (t.loss.kind == 0 && !t.loss.betas))
+        return NPLDA_EINVAL;
+    return NPLDA_OK;
+}
+
+// The update kernel's request (UpdateArgs with its LossTail) from the model, loss and optimiser groups; ua.r, tail.partial,
+// tail.nblk and tail_here are the caller's.  grad_only leaves the moments, the hyper-parameters and the loss address null or
+// zero, where the kernels do not look:
+//   train_update_kernel reads a.m / a.v behind `a.grad_only ? 0.f :` only, and stores moments, parameters and the image
+//     only past `if (a.grad_only) continue;`;
+//   loss_tail_block (nplda_loss_tail.h) leaves at `if (a.sums_out) { ... return; }`, in front of every use of a.loss,
+//     a.loss_sum, a.gout, a.m, a.v and the thresholds' update.
+//   (Both form Adam's constants from step[0] and the five scalars first: `step` stays required, the zeros are arithmetic.)
+static int fill_update(UpdateArgs& ua, const TrainStep& t, int nth) {
+    const size_t ngrad = nplda_grad_floats(t.net.D0, t.net.D1, t.net.D2);
+    LossTail& tl = ua.tail;
+    for (int k = 0; k < nth; ++k) {
+        if (!t.loss.thetas[k]) return NPLDA_EINVAL;
+        tl.theta[k] = t.loss.thetas[k];
+        if (t.loss.kind == 0) tl.beta.b[k] = t.loss.betas[k];
+    }
+    tl.K = nth; tl.kind = t.loss.kind; tl.alpha = t.loss.alpha;
+    for (int i = 0; i < 6; ++i) ua.prm[i] = t.net.params[i];
+    ua.r.D0 = t.net.D0; ua.r.D1 = t.net.D1; ua.r.D2 = t.net.D2;
+    ua.L = nplda_layout(t.net.D0, t.net.D1, t.net.D2); ua.packed = (float*)t.net.packed;
+    tl.step = ua.step = t.opt.step;
+    ua.bumped = tl.bumped = 1;  // the step's first kernel has counted the step
+    ua.ngrad_blocks = (unsigned)((ngrad + 256 * kUpdateE - 1) / (256 * kUpdateE));
+    if (t.grad_only) {
+        ua.grad_only = 1;
+        tl.sums_out = t.flat + ngrad;
+        return NPLDA_OK;
+    }
+    const TrainStep::Optim& o = t.opt;
+    ua.m = o.exp_avg; ua.v = o.exp_avg_sq; tl.m = o.exp_avg + ngrad; tl.v = o.exp_avg_sq + ngrad;
+    ua.lr = tl.lr = o.lr; ua.beta1 = tl.beta1 = o.beta1; ua.beta2 = tl.beta2 = o.beta2; ua.eps = tl.eps = o.eps;
+    ua.wd = tl.wd = o.wd;
+    tl.loss = t.out.loss; tl.loss_sum = t.out.loss_sum; tl.gout = t.out.grad_out ? t.out.grad_out + ngrad : nullptr;
+    return NPLDA_OK;
+}
 }  // namespace
 
 size_t nplda_train_step_workspace_bytes(int64_t B, int D0, int D1, int D2) {
@@ -1391,90 +1491,77 @@ size_t nplda_train_step_rows_workspace_bytes(int64_t B, int D0, int D1, int D2) 
     return step_ws(B, nplda_layout(D0, D1, D2), true).total * sizeof(float);
 }
 
-static int train_step_impl(const float* x1, const float* x2, const int64_t* rows1, const int64_t* rows2, int64_t ntab,
-                           long long* cursor, void* stage, int64_t B, int64_t ldx, const float* target,
-                         float* const* params, int D0, int D1, int D2, float* const* thetas, const float* betas, int K,
-                         float alpha, int kind, float* exp_avg, float* exp_avg_sq, float* step, float lr, float beta1,
-                         float beta2, float eps, float weight_decay, void* packed, void* ws, size_t ws_bytes, float* loss,
-                         double* loss_sum, float* grad_out, nplda_stream_t stream, void* dxa = nullptr, void* dxb = nullptr,
-                         int64_t lddx = 0, bool io_bf16 = false, const double* gcount = nullptr, float* dp_flat = nullptr) {
-    // dp_flat: the data-parallel gradient phase (nplda_train_step_grad_f32) — same three launches, but the last two stop at
-    // this rank's flat gradient [ngrad | loss sums as kLossLimbs x kLossNS floats] and nothing is updated
-    if (dp_flat) {
-        if (cursor || grad_out) return NPLDA_EINVAL;
-        grad_out = dp_flat;
+static int train_step_impl(TrainStep t) {
+    TrainStep::Batch& in = t.in;
+    if (t.grad_only && (in.cursor || t.out.grad_out)) return NPLDA_EINVAL;
+    if (in.cursor) {  // the batch sits in the staging record [rows1 | rows2 | labels]
+        if (!in.stage || !nplda_aligned16(in.stage) || in.B < 1) return NPLDA_EINVAL;
+        if ((in.B % 4) != 0) return NPLDA_EUNSUPPORTED;  // 16-byte pieces: the labels sit behind 16 B bytes of indices
+        in.rows1 = (const int64_t*)in.stage;
+        in.rows2 = in.rows1 + in.B;
+        in.target = (const float*)(in.rows2 + in.B);
     }
-    if (cursor) {  // the batch sits in the staging record [rows1 | rows2 | labels]
-        if (!stage || !nplda_aligned16(stage) || B < 1) return NPLDA_EINVAL;
-        if ((B % 4) != 0) return NPLDA_EUNSUPPORTED;  // 16-byte pieces: the labels sit behind 16 B bytes of indices
-        rows1 = (const int64_t*)stage;
-        rows2 = rows1 + B;
-        target = (const float*)(rows2 + B);
-    }
+    const int64_t B = in.B;
     // staged form: the first kernel leaves fp32 copies of the x rows it read for the weight gradients — rows named by table
     // indices, or (io_bf16) the batch's own bfloat16 rows
-    const bool rows = rows1 != nullptr || io_bf16;
-    if (int rc = check_model(D0, D1, D2)) return rc;
-    if (rows1 && (!rows2 || ntab < 1)) return NPLDA_EINVAL;
-    if (rows && (D0 % 16) != 0) return NPLDA_EUNSUPPORTED;  // the staged rows are written k16-step by k16-step
-    if (io_bf16 && (D0 != 512 || rows1)) return NPLDA_EUNSUPPORTED;
-    if ((dxa == nullptr) != (dxb == nullptr) || (dxa && lddx < D0)) return NPLDA_EINVAL;
+    const bool rows = in.rows1 != nullptr || in.io_bf16;
+    if (int rc = check_model(t.net.D0, t.net.D1, t.net.D2)) return rc;
+    if (in.rows1 && (!in.rows2 || in.ntab < 1)) return NPLDA_EINVAL;
+    if (rows && (t.net.D0 % 16) != 0) return NPLDA_EUNSUPPORTED;  // the staged rows are written k16-step by k16-step
+    if (in.io_bf16 && (t.net.D0 != 512 || in.rows1)) return NPLDA_EUNSUPPORTED;
+    if ((t.out.dxa == nullptr) != (t.out.dxb == nullptr) || (t.out.dxa && t.out.lddx < t.net.D0)) return NPLDA_EINVAL;
     if (B < 1) return NPLDA_EINVAL;
     if (B > 16 * 1024) return NPLDA_EUNSUPPORTED;  // larger batches: the separate launches (two-pass loss)
-    if (kind != 0 && kind != 1) return kind == 2 ? NPLDA_EUNSUPPORTED : NPLDA_EINVAL;
-    const int nth = kind == 1 ? 1 : K;
-    if (nth < 1 || nth > nplda_loss::kMaxK || !thetas || !params || (kind == 0 && !betas)) return NPLDA_EINVAL;
-    if (!target || !exp_avg || !exp_avg_sq || !step || !packed || !ws || !loss) return NPLDA_EINVAL;
-    if (!nplda_aligned16(packed) || !nplda_aligned16(ws) || !nplda_aligned16(target)) return NPLDA_EINVAL;
-    if (!rows_ok(x1, ldx, D0) || !rows_ok(x2, ldx, D0)) return NPLDA_EINVAL;
+    int nth = 0;
+    if (int rc = check_loss_spec(t, &nth)) return rc;
+    if (!in.target || !t.opt.step || !t.net.packed || !t.net.ws) return NPLDA_EINVAL;
+    if (!t.grad_only && (!t.opt.exp_avg || !t.opt.exp_avg_sq || !t.out.loss)) return NPLDA_EINVAL;  // (see fill_update)
+    if (!nplda_aligned16(t.net.packed) || !nplda_aligned16(t.net.ws) || !nplda_aligned16(in.target)) return NPLDA_EINVAL;
+    if (!rows_ok(in.x1, in.ldx, t.net.D0) || !rows_ok(in.x2, in.ldx, t.net.D0)) return NPLDA_EINVAL;
     for (int i = 0; i < 6; ++i)
-        if (!params[i]) return NPLDA_EINVAL;
-    const NpldaLayout L = nplda_layout(D0, D1, D2);
+        if (!t.net.params[i]) return NPLDA_EINVAL;
+    const NpldaLayout L = nplda_layout(t.net.D0, t.net.D1, t.net.D2);
     const StepWs S = step_ws(B, L, rows);
-    if (ws_bytes < S.total * sizeof(float)) return NPLDA_ENOSPC;
-    hipStream_t st = (hipStream_t)stream;
-    float* wsf = (float*)ws;
+    if (t.net.ws_bytes < S.total * sizeof(float)) return NPLDA_ENOSPC;
+    hipStream_t st = (hipStream_t)t.stream;
+    float* wsf = (float*)t.net.ws;
 
-    BwdLoss ls = {};
-    ls.s = wsf + S.s; ls.t = target; ls.K = nth; ls.kind = kind; ls.alpha = alpha; ls.B = B;
-    ls.g_out = wsf + S.g; ls.partial = reinterpret_cast<double*>(wsf + S.partial);
-    ls.gcount = gcount;
     UpdateArgs ua = {};
-    for (int k = 0; k < nth; ++k) {
-        if (!thetas[k]) return NPLDA_EINVAL;
-        ls.th.p[k] = thetas[k];
-        ua.tail.theta[k] = thetas[k];
-        if (kind == 0) ls.beta.b[k] = betas[k];
-    }
+    if (int rc = fill_update(ua, t, nth)) return rc;
+    BwdLoss ls = {};
+    ls.s = wsf + S.s; ls.t = in.target; ls.K = nth; ls.kind = t.loss.kind; ls.alpha = t.loss.alpha; ls.B = B;
+    ls.g_out = wsf + S.g; ls.partial = reinterpret_cast<double*>(wsf + S.partial);
+    ls.gcount = t.loss.gcount; ls.beta = ua.tail.beta;
+    for (int k = 0; k < nth; ++k) ls.th.p[k] = t.loss.thetas[k];
     const WsLayout W = ws_layout(2 * B, L, false);
     float* bws = wsf + S.bwd;
     bool dx_fused = false, x_direct = false;
     int nrows = (int)((B + 15) / 16);  // rows of pair sums / loss partials the first kernel leaves
     {   // forward + loss + data gradients: one kernel (nplda_train_fb_small.h; at the recipe shapes nplda_train_fb_half.h)
         TrainFbArgs fb = {};
-        fb.xa = x1; fb.xb = x2; fb.n = B; fb.ldx = ldx; fb.packed = (const float*)packed; fb.D0 = L.D0; fb.KS1 = L.KS1;
-        fb.oW2 = L.oW2; fb.oW2T = L.oW2T; fb.ob1 = L.ob1; fb.ob2 = L.ob2; fb.oQ = L.oQ; fb.oP = L.oP;
+        fb.xa = in.x1; fb.xb = in.x2; fb.n = B; fb.ldx = in.ldx; fb.packed = (const float*)t.net.packed;
+        fb.D0 = L.D0; fb.KS1 = L.KS1; fb.oW2 = L.oW2; fb.oW2T = L.oW2T; fb.ob1 = L.ob1; fb.ob2 = L.ob2; fb.oQ = L.oQ; fb.oP = L.oP;
         fb.out_s = wsf + S.s; fb.out_y = wsf + S.y; fb.dz = bws + W.dz; fb.du = bws + W.du; fb.ldz = S.ldz;
-        fb.pq = bws + W.pq; fb.ls = ls; fb.step_bump = step;
+        fb.pq = bws + W.pq; fb.ls = ls; fb.step_bump = t.opt.step;
         if (rows) {
-            fb.ia = (const long long*)rows1; fb.ib = (const long long*)rows2; fb.ntab = rows1 ? ntab : B;
-            fb.rec_bump = cursor ? cursor + 1 : nullptr;
+            fb.ia = (const long long*)in.rows1; fb.ib = (const long long*)in.rows2; fb.ntab = in.rows1 ? in.ntab : B;
+            fb.rec_bump = in.cursor ? in.cursor + 1 : nullptr;
             // bf16 rows of the batch itself: the weight-gradient kernel reads them as they are (widened in registers) — no
             // fp32 copy staged here, 16.8 MB less left dirty behind this kernel at B = 4096
-            x_direct = io_bf16 && !rows1 && wgrad_fm_bf16_ok(B, ldx, L);
+            x_direct = in.io_bf16 && !in.rows1 && wgrad_fm_bf16_ok(B, in.ldx, L);
             if (!x_direct) { fb.xsa = wsf + S.xs; fb.xsb = wsf + S.xs + (size_t)B * S.ldxs; fb.ldxs = S.ldxs; }
         }
         const dim3 grid((unsigned)((B + 15) / 16)), block(256);
         const bool k32 = L.KS1 == 32 && L.D0 == 512;
-        if (io_bf16 && !(k32 && L.NB >= 10)) return NPLDA_EUNSUPPORTED;
+        if (in.io_bf16 && !(k32 && L.NB >= 10)) return NPLDA_EUNSUPPORTED;
         // dL/dx inside the first kernel (its DX form) at the recipe shapes: no dx launch, du is not read back
-        dx_fused = dxa != nullptr && k32 && L.NB >= 10;
-        if (dx_fused) { fb.oW1T = L.oW1T; fb.dx0 = dxa; fb.dx1 = dxb; fb.lddx = lddx; }
+        dx_fused = t.out.dxa != nullptr && k32 && L.NB >= 10;
+        if (dx_fused) { fb.oW1T = L.oW1T; fb.dx0 = t.out.dxa; fb.dx1 = t.out.dxb; fb.lddx = t.out.lddx; }
 #define NPLDA_LAUNCH(NBV)                                                                                   \
-    if (dx_fused && io_bf16) hipLaunchKernelGGL((train_fb_small_kernel<(NBV >= 10 ? NBV : 10), 32, true, true, 2>), grid, block, 0, st, fb); \
+    if (dx_fused && in.io_bf16) hipLaunchKernelGGL((train_fb_small_kernel<(NBV >= 10 ? NBV : 10), 32, true, true, 2>), grid, block, 0, st, fb); \
     else if (dx_fused && rows) hipLaunchKernelGGL((train_fb_small_kernel<(NBV >= 10 ? NBV : 10), 32, true, false, 1>), grid, block, 0, st, fb); \
     else if (dx_fused) hipLaunchKernelGGL((train_fb_small_kernel<(NBV >= 10 ? NBV : 10), 32, false, false, 1>), grid, block, 0, st, fb); \
-    else if (io_bf16) hipLaunchKernelGGL((train_fb_small_kernel<(NBV >= 10 ? NBV : 10), 32, true, true>), grid, block, 0, st, fb); \
+    else if (in.io_bf16) hipLaunchKernelGGL((train_fb_small_kernel<(NBV >= 10 ? NBV : 10), 32, true, true>), grid, block, 0, st, fb); \
     else if (k32 && rows) hipLaunchKernelGGL((train_fb_small_kernel<NBV, 32, true>), grid, block, 0, st, fb);      \
     else if (k32) hipLaunchKernelGGL((train_fb_small_kernel<NBV, 32, false>), grid, block, 0, st, fb);        \
     else if (rows) hipLaunchKernelGGL((train_fb_small_kernel<NBV, 0, true>), grid, block, 0, st, fb);         \
@@ -1485,10 +1572,10 @@ static int train_step_impl(const float* x1, const float* x2, const int64_t* rows
             nrows = (int)((B + kHalfPairs - 1) / kHalfPairs);
             const dim3 hgrid((unsigned)((B + kHalfPairs - 1) / kHalfPairs));
 #define NPLDA_LAUNCH_H(NBV)                                                                                                 \
-    if (dx_fused && io_bf16) hipLaunchKernelGGL((train_fb_half_kernel<NBV, true, true, 2>), hgrid, block, 0, st, fb, skew);   \
+    if (dx_fused && in.io_bf16) hipLaunchKernelGGL((train_fb_half_kernel<NBV, true, true, 2>), hgrid, block, 0, st, fb, skew);   \
     else if (dx_fused && rows) hipLaunchKernelGGL((train_fb_half_kernel<NBV, true, false, 1>), hgrid, block, 0, st, fb, skew); \
     else if (dx_fused) hipLaunchKernelGGL((train_fb_half_kernel<NBV, false, false, 1>), hgrid, block, 0, st, fb, skew);      \
-    else if (io_bf16) hipLaunchKernelGGL((train_fb_half_kernel<NBV, true, true>), hgrid, block, 0, st, fb, skew);            \
+    else if (in.io_bf16) hipLaunchKernelGGL((train_fb_half_kernel<NBV, true, true>), hgrid, block, 0, st, fb, skew);            \
     else if (rows) hipLaunchKernelGGL((train_fb_half_kernel<NBV, true>), hgrid, block, 0, st, fb, skew);                     \
     else hipLaunchKernelGGL((train_fb_half_kernel<NBV, false>), hgrid, block, 0, st, fb, skew)
             if (L.NB == 10) { NPLDA_LAUNCH_H(10); } else { NPLDA_LAUNCH_H(11); }
@@ -1507,51 +1594,35 @@ static int train_step_impl(const float* x1, const float* x2, const int64_t* rows
 #undef NPLDA_LAUNCH
         if (int rc = nplda_launch_status()) return rc;
     }
-    {   // the loss / threshold tail: in the weight-gradient launch where the full-M kernel runs, else in the update kernel
-        LossTail& t = ua.tail;
-        const size_t ngrad0 = nplda_grad_floats(D0, D1, D2);
-        t.partial = ls.partial; t.nblk = nrows; t.K = nth; t.kind = kind; t.beta = ls.beta; t.alpha = alpha;
-        t.loss = loss; t.loss_sum = loss_sum; t.m = exp_avg + ngrad0; t.v = exp_avg_sq + ngrad0;
-        t.gout = grad_out ? grad_out + ngrad0 : nullptr; t.step = step; t.bumped = 1;
-        t.lr = lr; t.beta1 = beta1; t.beta2 = beta2; t.eps = eps; t.wd = weight_decay;
-        if (dp_flat) { t.sums_out = dp_flat + ngrad0; t.gout = nullptr; t.loss_sum = nullptr; }
-    }
-    ua.grad_only = dp_flat ? 1 : 0;
+    // the loss / threshold tail: in the weight-gradient launch where the full-M kernel runs, else in the update kernel
+    ua.tail.partial = ls.partial; ua.tail.nblk = nrows;
     bool tail_done = false;
     // the weight gradients read the x rows: the caller's, or the ones the first kernel gathered
     const bool staged = rows && !x_direct;
-    const float* wx1 = staged ? wsf + S.xs : x1;
-    const float* wx2 = staged ? wsf + S.xs + (size_t)B * S.ldxs : x2;
-    if (int rc = backward_launch(false, wx1, wx2, 2 * B, B, staged ? S.ldxs : ldx, (const float*)packed, L, nullptr,
-                                 wsf + S.y, wsf + S.z, wsf + S.rn, S.ldz, params[4], bws, W, grad_out, nullptr, nullptr, 0,
-                                 st, &ls, &ua.r, true, &ua.tail, &tail_done, x_direct, nrows))
-        return rc;
-    if (dxa && !dx_fused) {  // dL/dx = du . W1 with the weights the forward used (the update below comes after)
+    BwdRequest q = {};
+    q.xa = staged ? wsf + S.xs : in.x1; q.xb = staged ? wsf + S.xs + (size_t)B * S.ldxs : in.x2;
+    q.K = 2 * B; q.nsplit = B; q.ldx = staged ? S.ldxs : in.ldx; q.x_bf16 = x_direct;
+    q.y = wsf + S.y; q.z = wsf + S.z; q.rn = wsf + S.rn; q.ldz = S.ldz;
+    q.packed = (const float*)t.net.packed; q.L = L; q.P_sqrt = t.net.params[4]; q.wsf = bws; q.W = W;
+    q.grad_flat = t.grad_only ? t.flat : t.out.grad_out; q.st = st;
+    q.fused.ls = &ls; q.fused.defer_reduce = &ua.r; q.fused.data_done = true; q.fused.pq_rows = nrows;
+    q.fused.tail = &ua.tail; q.fused.tail_done = &tail_done;
+    if (int rc = backward_launch(q)) return rc;
+    if (t.out.dxa && !dx_fused) {  // dL/dx = du . W1 with the weights the forward used (the update below comes after)
         // (Measured and NOT kept, round 4: this launch on a side stream, forked behind the first kernel and joined in front of
         // the update — two branches of the captured graph.  The weight-gradient blocks (512 threads, 90 KB of LDS) and these
         // do not share a CU to any effect: cfg5 0.0820 -> 0.0810 ms, not worth a library that creates streams.)
-        if (int rc = input_grad_from_du(bws + W.du, 2 * B, S.ldz, (const float*)packed, L, nullptr, dxa, dxb, B, lddx, st, io_bf16))
+        if (int rc = input_grad_from_du(bws + W.du, 2 * B, S.ldz, q.packed, L, nullptr, t.out.dxa, t.out.dxb, B, t.out.lddx,
+                                        st, in.io_bf16))
             return rc;
     }
-    for (int i = 0; i < 6; ++i) ua.prm[i] = params[i];
-    ua.m = exp_avg; ua.v = exp_avg_sq; ua.step = step;
-    ua.lr = lr; ua.beta1 = beta1; ua.beta2 = beta2; ua.eps = eps; ua.wd = weight_decay;
-    ua.L = L; ua.packed = (float*)packed;
-    ua.bumped = 1;
     ua.tail_here = tail_done ? 0 : 1;
-    if (cursor) {
-        ua.cursor = cursor; ua.stage = (char*)stage; ua.rec_bytes = 20 * (long long)B;
+    if (in.cursor) {
+        ua.cursor = in.cursor; ua.stage = (char*)in.stage; ua.rec_bytes = 20 * (long long)B;
         ua.ncopy = (unsigned)((ua.rec_bytes / 16 + 255) / 256);
         if (ua.ncopy > 32) ua.ncopy = 32;
     }
-    const size_t ngrad = nplda_grad_floats(D0, D1, D2);
-#ifndef NPLDA_UPDATE_E
-#define NPLDA_UPDATE_E 2
-#endif
-    constexpr int E = NPLDA_UPDATE_E;  // without arrival tickets (the first kernel has counted the step) small blocks are free
-    ua.ngrad_blocks = (unsigned)((ngrad + 256 * E - 1) / (256 * E));
-    hipLaunchKernelGGL(train_update_kernel<E>, dim3(ua.ngrad_blocks + (unsigned)ua.tail_here + ua.ncopy), dim3(256), 0, st, ua);
-    return nplda_launch_status();
+    return launch_update(ua, st);
 }
 
 int nplda_train_step_f32(const float* x1, const float* x2, int64_t B, int64_t ldx, const float* target,
@@ -1559,9 +1630,11 @@ int nplda_train_step_f32(const float* x1, const float* x2, int64_t B, int64_t ld
                          float alpha, int kind, float* exp_avg, float* exp_avg_sq, float* step, float lr, float beta1,
                          float beta2, float eps, float weight_decay, void* packed, void* ws, size_t ws_bytes, float* loss,
                          double* loss_sum, float* grad_out, nplda_stream_t stream) {
-    return train_step_impl(x1, x2, nullptr, nullptr, 0, nullptr, nullptr, B, ldx, target, params, D0, D1, D2, thetas, betas, K, alpha, kind,
-                           exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, weight_decay, packed, ws, ws_bytes, loss,
-                           loss_sum, grad_out, stream);
+    TrainStep t = {};
+    t.in = {x1, x2, B, ldx, target};
+    t.net = {params, D0, D1, D2, packed, ws, ws_bytes}; t.loss = {thetas, betas, K, alpha, kind}; t.stream = stream;
+    t.opt = {exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, weight_decay}; t.out = {loss, loss_sum, grad_out};
+    return train_step_impl(t);
 }
 
 int nplda_train_step_dx_f32(const void* x1, const void* x2, int64_t B, int64_t ldx, int io_bf16, const float* target,
@@ -1570,9 +1643,11 @@ int nplda_train_step_dx_f32(const void* x1, const void* x2, int64_t B, int64_t l
                             float beta2, float eps, float weight_decay, void* packed, void* ws, size_t ws_bytes, float* loss,
                             double* loss_sum, float* grad_out, void* dx1, void* dx2, int64_t lddx, nplda_stream_t stream) {
     if (!dx1 || !dx2) return NPLDA_EINVAL;
-    return train_step_impl((const float*)x1, (const float*)x2, nullptr, nullptr, 0, nullptr, nullptr, B, ldx, target, params, D0,
-                           D1, D2, thetas, betas, K, alpha, kind, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps,
-                           weight_decay, packed, ws, ws_bytes, loss, loss_sum, grad_out, stream, dx1, dx2, lddx, io_bf16 != 0);
+    TrainStep t = {};
+    t.in = {(const float*)x1, (const float*)x2, B, ldx, target}; t.in.io_bf16 = io_bf16 != 0;
+    t.net = {params, D0, D1, D2, packed, ws, ws_bytes}; t.loss = {thetas, betas, K, alpha, kind}; t.stream = stream;
+    t.opt = {exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, weight_decay}; t.out = {loss, loss_sum, grad_out, dx1, dx2, lddx};
+    return train_step_impl(t);
 }
 
 int nplda_train_step_grad_f32(const float* x1, const float* x2, int64_t B, int64_t ldx, const float* target,
@@ -1580,11 +1655,9 @@ int nplda_train_step_grad_f32(const float* x1, const float* x2, int64_t B, int64
                               float* const* thetas, const float* betas, int K, float alpha, int kind, float* step,
                               void* packed, void* ws, size_t ws_bytes, float* flat, nplda_stream_t stream) {
     if (!flat) return NPLDA_EINVAL;
-    float dummy_loss = 0.f;  // (never written: the tail stops at the sums)
-    // the optimiser state is not touched in this phase; the moments' pointers only have to be non-null
-    return train_step_impl(x1, x2, nullptr, nullptr, 0, nullptr, nullptr, B, ldx, target, params, D0, D1, D2, thetas, betas, K,
-                           alpha, kind, flat, flat, step, 0.f, 0.f, 0.f, 0.f, 0.f, packed, ws, ws_bytes, &dummy_loss, nullptr,
-                           nullptr, stream, nullptr, nullptr, 0, false, global_counts, flat);
+    TrainStep t = grad_step({params, D0, D1, D2, packed, ws, ws_bytes}, {thetas, betas, K, alpha, kind, global_counts}, step, flat);
+    t.in = {x1, x2, B, ldx, target}; t.stream = stream;
+    return train_step_impl(t);
 }
 
 int nplda_train_step_grad_rows_f32(const float* table, int64_t N, int64_t ldt, const int64_t* rows1, const int64_t* rows2,
@@ -1592,10 +1665,9 @@ int nplda_train_step_grad_rows_f32(const float* table, int64_t N, int64_t ldt, c
                                    int D1, int D2, float* const* thetas, const float* betas, int K, float alpha, int kind,
                                    float* step, void* packed, void* ws, size_t ws_bytes, float* flat, nplda_stream_t stream) {
     if (!flat || !rows1 || !rows2 || N < 1) return NPLDA_EINVAL;
-    float dummy_loss = 0.f;
-    return train_step_impl(table, table, rows1, rows2, N, nullptr, nullptr, B, ldt, target, params, D0, D1, D2, thetas, betas, K,
-                           alpha, kind, flat, flat, step, 0.f, 0.f, 0.f, 0.f, 0.f, packed, ws, ws_bytes, &dummy_loss, nullptr,
-                           nullptr, stream, nullptr, nullptr, 0, false, global_counts, flat);
+    TrainStep t = grad_step({params, D0, D1, D2, packed, ws, ws_bytes}, {thetas, betas, K, alpha, kind, global_counts}, step, flat);
+    t.in = {table, table, B, ldt, target, rows1, rows2, N}; t.stream = stream;
+    return train_step_impl(t);
 }
 
 int nplda_train_step_grad_dx_f32(const void* x1, const void* x2, int64_t B, int64_t ldx, int io_bf16, const float* target,
@@ -1604,10 +1676,10 @@ int nplda_train_step_grad_dx_f32(const void* x1, const void* x2, int64_t B, int6
                                  void* packed, void* ws, size_t ws_bytes, float* flat, void* dx1, void* dx2, int64_t lddx,
                                  nplda_stream_t stream) {
     if (!flat || !dx1 || !dx2) return NPLDA_EINVAL;
-    float dummy_loss = 0.f;
-    return train_step_impl((const float*)x1, (const float*)x2, nullptr, nullptr, 0, nullptr, nullptr, B, ldx, target, params, D0,
-                           D1, D2, thetas, betas, K, alpha, kind, flat, flat, step, 0.f, 0.f, 0.f, 0.f, 0.f, packed, ws,
-                           ws_bytes, &dummy_loss, nullptr, nullptr, stream, dx1, dx2, lddx, io_bf16 != 0, global_counts, flat);
+    TrainStep t = grad_step({params, D0, D1, D2, packed, ws, ws_bytes}, {thetas, betas, K, alpha, kind, global_counts}, step, flat);
+    t.in = {(const float*)x1, (const float*)x2, B, ldx, target}; t.in.io_bf16 = io_bf16 != 0;
+    t.out.dxa = dx1; t.out.dxb = dx2; t.out.lddx = lddx; t.stream = stream;
+    return train_step_impl(t);
 }
 
 size_t nplda_train_step_flat_floats(int D0, int D1, int D2) {
@@ -1619,39 +1691,21 @@ int nplda_train_step_apply_f32(const float* flat, float* const* params, int D0, 
                                const float* betas, int K, float alpha, int kind, float* exp_avg, float* exp_avg_sq,
                                float* step, float lr, float beta1, float beta2, float eps, float weight_decay, void* packed,
                                float* loss, double* loss_sum, nplda_stream_t stream) {
+    TrainStep t = {};
+    t.net = {params, D0, D1, D2, packed}; t.loss = {thetas, betas, K, alpha, kind};
+    t.opt = {exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, weight_decay}; t.out = {loss, loss_sum};
     if (int rc = check_model(D0, D1, D2)) return rc;
-    if (kind != 0 && kind != 1) return kind == 2 ? NPLDA_EUNSUPPORTED : NPLDA_EINVAL;
-    const int nth = kind == 1 ? 1 : K;
-    if (nth < 1 || nth > nplda_loss::kMaxK || !thetas || !params || (kind == 0 && !betas)) return NPLDA_EINVAL;
+    int nth = 0;
+    if (int rc = check_loss_spec(t, &nth)) return rc;
     if (!flat || !exp_avg || !exp_avg_sq || !step || !packed || !loss || !nplda_aligned16(packed)) return NPLDA_EINVAL;
-    const NpldaLayout L = nplda_layout(D0, D1, D2);
-    const size_t ngrad = nplda_grad_floats(D0, D1, D2);
-    UpdateArgs ua = {};
-    ua.r.D0 = D0; ua.r.D1 = D1; ua.r.D2 = D2;
-    for (int i = 0; i < 6; ++i) {
+    for (int i = 0; i < 6; ++i)
         if (!params[i]) return NPLDA_EINVAL;
-        ua.prm[i] = params[i];
-    }
-    LossTail& t = ua.tail;
-    for (int k = 0; k < nth; ++k) {
-        if (!thetas[k]) return NPLDA_EINVAL;
-        t.theta[k] = thetas[k];
-        if (kind == 0) t.beta.b[k] = betas[k];
-    }
-    t.nblk = 0; t.K = nth; t.kind = kind; t.alpha = alpha; t.loss = loss; t.loss_sum = loss_sum;
-    t.m = exp_avg + ngrad; t.v = exp_avg_sq + ngrad; t.step = step; t.bumped = 1;
-    t.lr = lr; t.beta1 = beta1; t.beta2 = beta2; t.eps = eps; t.wd = weight_decay;
-    t.sums_in = flat + ngrad;
-    ua.m = exp_avg; ua.v = exp_avg_sq; ua.step = step;
-    ua.lr = lr; ua.beta1 = beta1; ua.beta2 = beta2; ua.eps = eps; ua.wd = weight_decay;
-    ua.L = L; ua.packed = (float*)packed;
-    ua.bumped = 1;  // nplda_train_step_grad_f32's first kernel has counted the step
+    UpdateArgs ua = {};
+    if (int rc = fill_update(ua, t, nth)) return rc;
+    // the gradient and the loss sums come from the all-reduced flat buffer: no slabs, no loss partials
+    ua.flat = flat; ua.tail.sums_in = flat + nplda_grad_floats(D0, D1, D2);
     ua.tail_here = 1;
-    ua.flat = flat;
-    constexpr int E = 2;
-    ua.ngrad_blocks = (unsigned)((ngrad + 256 * E - 1) / (256 * E));
-    hipLaunchKernelGGL(train_update_kernel<E>, dim3(ua.ngrad_blocks + 1), dim3(256), 0, (hipStream_t)stream, ua);
-    return nplda_launch_status();
+    return launch_update(ua, (hipStream_t)stream);
 }
 
 size_t nplda_train_step_dx_workspace_bytes(int64_t B, int D0, int D1, int D2, int io_bf16) {
@@ -1666,9 +1720,11 @@ int nplda_train_step_rows_f32(const float* table, int64_t N, int64_t ldt, const 
                               float weight_decay, void* packed, void* ws, size_t ws_bytes, float* loss, double* loss_sum,
                               float* grad_out, nplda_stream_t stream) {
     if (!rows1 || !rows2 || N < 1) return NPLDA_EINVAL;
-    return train_step_impl(table, table, rows1, rows2, N, nullptr, nullptr, B, ldt, target, params, D0, D1, D2, thetas, betas, K, alpha, kind,
-                           exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, weight_decay, packed, ws, ws_bytes, loss,
-                           loss_sum, grad_out, stream);
+    TrainStep t = {};
+    t.in = {table, table, B, ldt, target, rows1, rows2, N};
+    t.net = {params, D0, D1, D2, packed, ws, ws_bytes}; t.loss = {thetas, betas, K, alpha, kind}; t.stream = stream;
+    t.opt = {exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, weight_decay}; t.out = {loss, loss_sum, grad_out};
+    return train_step_impl(t);
 }
 
 int nplda_train_step_records_f32(const float* table, int64_t N, int64_t ldt, int64_t* cursor, void* stage, int64_t B,
@@ -1677,9 +1733,11 @@ int nplda_train_step_records_f32(const float* table, int64_t N, int64_t ldt, int
                                  float beta1, float beta2, float eps, float weight_decay, void* packed, void* ws,
                                  size_t ws_bytes, float* loss, double* loss_sum, float* grad_out, nplda_stream_t stream) {
     if (!cursor || !stage || N < 1) return NPLDA_EINVAL;
-    return train_step_impl(table, table, nullptr, nullptr, N, (long long*)cursor, stage, B, ldt, nullptr, params, D0, D1, D2, thetas,
-                           betas, K, alpha, kind, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, weight_decay, packed, ws,
-                           ws_bytes, loss, loss_sum, grad_out, stream);
+    TrainStep t = {};
+    t.in = {table, table, B, ldt}; t.in.ntab = N; t.in.cursor = (long long*)cursor; t.in.stage = stage;
+    t.net = {params, D0, D1, D2, packed, ws, ws_bytes}; t.loss = {thetas, betas, K, alpha, kind}; t.stream = stream;
+    t.opt = {exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, weight_decay}; t.out = {loss, loss_sum, grad_out};
+    return train_step_impl(t);
 }
 
 size_t nplda_lda_wgrad_workspace_bytes(int64_t B, int D0, int D1) {
@@ -1695,10 +1753,7 @@ int nplda_lda_wgrad_f32(const float* x1, const float* x2, int64_t B, int64_t ldx
     if (!out) return NPLDA_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const size_t nout = (size_t)D1 * D0 + D1;
-    if (B == 0) {
-        hipError_t e = hipMemsetAsync(out, 0, nout * sizeof(float), st);
-        return e == hipSuccess ? NPLDA_OK : (int)e;
-    }
+    if (B == 0) return zero_gradient(out, nout, st);
     const NpldaLayout L = nplda_layout(D0, D1, D1);
     const WsLayout W = ws_layout(2 * B, L, false);
     if (!ws || !nplda_aligned16(ws) || !rows_ok(x1, ldx, D0) || !rows_ok(x2, ldx, D0) || !rows_ok(du, ldz, W.Mp))
@@ -1709,12 +1764,9 @@ int nplda_lda_wgrad_f32(const float* x1, const float* x2, int64_t B, int64_t ldx
     WgradArgs wa = {};
     wa.K = 2 * B; wa.nsplit = B; wa.ksplit = W.ksplit; wa.rows_per_split = W.rows_per_split;
     wa.ldz = ldz; wa.ext = ext; wa.Mp = W.Mp;
-    WgradProblem& p1 = wa.p[0];
-    p1.A = du; p1.lda = ldz; p1.B0 = x1; p1.B1 = x2; p1.ldb = ldx; p1.M = W.Mp; p1.N = D0;
-    p1.MT = (W.Mp + 63) / 64; p1.NT = (D0 + 63) / 64; p1.slab = slab; p1.Mp = W.Mp; p1.Np = W.Np1; p1.extras = 1;
-    wa.p[1] = p1;  // never scheduled (nw == nw0)
-    wa.nw0 = p1.MT * p1.NT * W.ksplit;
-    wa.nw = wa.nw_mm = wa.nw_ps = wa.nw0;
+    WgradProblem& p1 = wa.p[0] = wgrad_problem(W.Mp, D0, W.Np1, 1);
+    p1.A = du; p1.lda = ldz; p1.B0 = x1; p1.B1 = x2; p1.ldb = ldx; p1.slab = slab;
+    wgrad_count(wa, 1, false);
     if (int rc = wgrad_launch(wa, L.NB, 1, st)) return rc;
     ReduceArgs ra = {};
     ra.slab1 = slab; ra.slab2 = slab; ra.ext = ext; ra.P_sqrt = nullptr;
