@@ -24,6 +24,8 @@
 //                           Output (mean, std, mean_top, std_top), population std (ddof = 0), fp64.
 //  K9  asnorm_apply_kernel  per trial: z-norm, t-norm, s-norm, as-norm1 from the two rows' statistics
 //                           (adaptive_score_normalization.py:65-73), fp64, ~100 B/trial: HBM-bound.
+#include <initializer_list>
+
 #include "nplda_common.h"
 #include "nplda_cohort_common.h"
 #include "nplda_cohort_fused.h"
@@ -848,8 +850,6 @@ extern "C" {
 // the workspace starts with the tile counters of the GEMM (one per XCD), the spilled score rows follow
 static constexpr size_t kCohortCtlBytes = 256;
 
-static constexpr int kFallbackBlocks = 64;
-
 static size_t spill_workspace_bytes(int64_t R, int64_t M) {
     // whole matrix if it is below 4 GiB, else row chunks of at least 128 rows
     const unsigned long long row = ((unsigned long long)M + 3) / 4 * 4 * sizeof(float);
@@ -863,46 +863,33 @@ static size_t spill_workspace_bytes(int64_t R, int64_t M) {
     return (size_t)(rows * row) + kCohortCtlBytes;
 }
 
-// workspace of the fused path for `rows` rows (a multiple of 128): fixed part + per-row arrays + the fallback's scratch rows
-static size_t fused_workspace_bytes(const nplda::FusedPlan& p, long long rows, long long M) {
-    const size_t lds = (size_t)((M + 3) / 4 * 4);
-    return p.fixed_bytes + (size_t)rows * p.row_bytes + (size_t)kFallbackBlocks * lds * sizeof(float) + 256;
+// Workspace for R rows: the fused path's (no score matrix, a few KB per row; like the spilled matrix at most 4 GiB, the table is
+// then chunked) where the shape is eligible, else the spilled matrix — which spill_floor keeps as a lower bound either way.
+static size_t cohort_workspace_need(int64_t R, int64_t M, int topn, int Mp, bool spill_floor) {
+    const size_t spill = spill_workspace_bytes(R, M);
+    const nplda::FusedPlan p = nplda::cohort_fused_plan(M, topn, Mp);
+    if (!p.eligible) return spill;
+    long long rows = (R + 127) / 128 * 128;
+    const long long cap_rows = nplda::fused_rows_cap(p, 4ull << 30, M);
+    if (rows > cap_rows) rows = cap_rows;
+    const size_t fused = nplda::fused_workspace_bytes(p, rows, M);
+    return spill_floor && spill > fused ? spill : fused;
 }
 
 size_t nplda_cohort_workspace_bytes(int64_t R, int64_t M) {
     if (R <= 0 || M <= 0) return 0;
-    size_t need = spill_workspace_bytes(R, M);
-    // the fused path (no score matrix) for the default top-N: its workspace is a few KB per row
-    const nplda::FusedPlan p = nplda::cohort_fused_plan(M, 500, NPLDA_MAX_DIM);
-    if (p.eligible) {
-        long long rows = (R + 127) / 128 * 128;
-        if (rows > p.max_rows) rows = p.max_rows;
-        const long long cap_rows = (long long)(((4ull << 30) - fused_workspace_bytes(p, 0, M)) / p.row_bytes) / 128 * 128;
-        if (rows > cap_rows) rows = cap_rows;  // like the spilled matrix: at most 4 GiB, the table is then chunked
-        const size_t f = fused_workspace_bytes(p, rows, M);
-        if (f > need) need = f;
-    }
-    return need;
+    return cohort_workspace_need(R, M, 500, NPLDA_MAX_DIM, true);  // the default top-N at the widest model, either path
 }
 
 size_t nplda_cohort_workspace_bytes_ex(int64_t R, int64_t M, int topn, int D1, int D2) {
     if (R <= 0 || M <= 0 || nplda_kernel_nb(D1, D2) == 0) return 0;
-    size_t need = spill_workspace_bytes(R, M);
-    const nplda::FusedPlan p = nplda::cohort_fused_plan(M, topn, 16 * nplda_kernel_nb(D1, D2));
-    if (p.eligible) {
-        long long rows = (R + 127) / 128 * 128;
-        if (rows > p.max_rows) rows = p.max_rows;
-        const long long cap_rows = (long long)(((4ull << 30) - fused_workspace_bytes(p, 0, M)) / p.row_bytes) / 128 * 128;
-        if (rows > cap_rows) rows = cap_rows;
-        need = fused_workspace_bytes(p, rows, M);  // the fused path never needs the score matrix
-    }
-    return need;
+    return cohort_workspace_need(R, M, topn, 16 * nplda_kernel_nb(D1, D2), false);  // the fused path never needs the score matrix
 }
 
 size_t nplda_cohort_fused_min_workspace_bytes(int64_t M, int topn, int D1, int D2) {
     if (M <= 0 || nplda_kernel_nb(D1, D2) == 0) return 0;
     const nplda::FusedPlan p = nplda::cohort_fused_plan(M, topn, 16 * nplda_kernel_nb(D1, D2));
-    return p.eligible ? fused_workspace_bytes(p, 128, M) : 0;
+    return p.eligible ? nplda::fused_workspace_bytes(p, 128, M) : 0;
 }
 
 size_t nplda_cohort_state_bytes(int64_t M, int topn, int D1, int D2) {
@@ -911,25 +898,132 @@ size_t nplda_cohort_state_bytes(int64_t M, int topn, int D1, int D2) {
     return p.eligible ? p.fixed_bytes : 0;
 }
 
+// The checks the cohort entry points share, in the order that is part of the ABI: the counts, then the model (EINVAL before
+// EUNSUPPORTED) ...
+static int check_counts_and_model(bool counts_ok, int D0, int D1, int D2) {
+    if (!counts_ok) return NPLDA_EINVAL;
+    if (D0 <= 0 || D1 <= 0 || D2 <= 0 || (D0 % 4) != 0) return NPLDA_EINVAL;
+    return nplda_dims_ok(D0, D1, D2) ? NPLDA_OK : NPLDA_EUNSUPPORTED;
+}
+// ... and, once the model is known, the pointers and the tables' row stride (all EINVAL)
+static int check_tables(std::initializer_list<const void*> required, std::initializer_list<const void*> aligned16, int64_t ldz,
+                        int NB) {
+    for (const void* p : required)
+        if (!p) return NPLDA_EINVAL;
+    if (ldz < 16 * NB || (ldz % 4) != 0) return NPLDA_EINVAL;
+    for (const void* p : aligned16)
+        if (!nplda_aligned16(p)) return NPLDA_EINVAL;
+    return NPLDA_OK;
+}
+
 int nplda_cohort_prepare_f32(const float* z_coh, const float* q_coh, int64_t M, int64_t ldz, const void* packed, int D0, int D1,
                              int D2, int topn, void* state, size_t state_bytes, nplda_stream_t stream) {
-    if (M <= 0 || topn < 1 || M > 0x7ffffff0LL) return NPLDA_EINVAL;
-    if (D0 <= 0 || D1 <= 0 || D2 <= 0 || (D0 % 4) != 0) return NPLDA_EINVAL;
-    if (!nplda_dims_ok(D0, D1, D2)) return NPLDA_EUNSUPPORTED;
+    if (int rc = check_counts_and_model(M > 0 && topn >= 1 && M <= 0x7ffffff0LL, D0, D1, D2)) return rc;
     const NpldaLayout L = nplda_layout(D0, D1, D2);
-    if (!z_coh || !q_coh || !packed || !state || ((uintptr_t)state & 255u) != 0) return NPLDA_EINVAL;
-    if (ldz < 16 * L.NB || (ldz % 4) != 0 || !nplda_aligned16(z_coh) || !nplda_aligned16(packed)) return NPLDA_EINVAL;
+    if (((uintptr_t)state & 255u) != 0) return NPLDA_EINVAL;
+    if (int rc = check_tables({z_coh, q_coh, packed, state}, {z_coh, packed}, ldz, L.NB)) return rc;
     const nplda::FusedPlan plan = nplda::cohort_fused_plan(M, topn, 16 * L.NB);
     if (!plan.eligible) return NPLDA_EUNSUPPORTED;
     if (state_bytes < plan.fixed_bytes) return NPLDA_ENOSPC;
-    return nplda::cohort_fused_prepare(plan, z_coh, q_coh, M, ldz, (const float*)packed + L.oP, L.NB, (unsigned char*)state,
-                                       (hipStream_t)stream);
+    return nplda::cohort_fused_prepare(plan, {z_coh, q_coh, M, ldz, nullptr}, {(const float*)packed + L.oP, L.NB, D2},
+                                       (unsigned char*)state, (hipStream_t)stream);
 }
 
+// Dynamic LDS of row_stats_kernel / cohort_fallback_kernel for rows of M scores: the row's keys when they fit (use_lds), the
+// count and sum partials, the shortcut's lists.  Above 64 KiB the kernels' limit is raised; rc: a HIP error from that.
+struct RowKernelLds { int use_lds; size_t shmem; int rc; };
+static RowKernelLds row_kernel_lds(int64_t M) {
+    RowKernelLds r = {M <= kMaxRowLds ? 1 : 0, 0, NPLDA_OK};
+    r.shmem = (r.use_lds ? (size_t)((M + 3) / 4 * 4) * 4 : 0) + 64 * 4 + (kRowThreads / 64) * 32 +
+              (2 * kListCap + 4 + 8 + kListCap / 2) * 4 + 16;
+    if (r.use_lds && r.shmem > 64 * 1024) {
+        for (const void* k : {(const void*)row_stats_kernel, (const void*)cohort_fallback_kernel}) {
+            const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.shmem);
+            if (e != hipSuccess) { r.rc = (int)e; break; }
+        }
+    }
+    return r;
+}
+
+// prepared: null, or the state of nplda_cohort_prepare_f32 (prepared_bytes of it)
 static int cohort_stats_impl(const float* z_rows, const float* q_rows, int64_t R, const float* z_coh,
                              const float* q_coh, int64_t M, int64_t ldz, const void* packed, int D0, int D1, int D2,
                              int topn, int select_lowest, double* stats, void* ws, size_t ws_bytes,
-                             nplda_stream_t stream, const void* prepared, size_t prepared_bytes);
+                             nplda_stream_t stream, const void* prepared, size_t prepared_bytes) {
+    if (int rc = check_counts_and_model(R >= 0 && M >= 0 && topn >= 1, D0, D1, D2)) return rc;
+    if (R == 0) return NPLDA_OK;
+    if (M == 0 || M > 0x7ffffff0LL) return NPLDA_EINVAL;
+    const NpldaLayout L = nplda_layout(D0, D1, D2);
+    if (int rc = check_tables({z_rows, q_rows, z_coh, q_coh, packed, stats, ws}, {z_rows, z_coh, packed, ws}, ldz, L.NB)) return rc;
+    const long long lds = (M + 3) / 4 * 4;
+    const size_t row_bytes = (size_t)lds * sizeof(float);
+    if (ws_bytes < kCohortCtlBytes + row_bytes) return NPLDA_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    const RowKernelLds rl = row_kernel_lds(M);
+    if (rl.rc) return rl.rc;
+    const float* P = (const float*)packed + L.oP;
+    const int lowest = select_lowest ? 1 : 0;
+
+    // ---- fused path: statistics in the GEMM's epilogue, no score matrix (nplda_cohort_fused.hip) -----------------------
+    // Chosen by the shape (M, top-N) alone, and every row is computed independently of its neighbours, so the result of
+    // a row does not depend on R, on the row's position or on how the workspace chunks the table.
+    const nplda::FusedPlan plan = nplda::cohort_fused_plan(M, topn, 16 * L.NB);
+    const bool fused = plan.eligible && ws_bytes >= nplda::fused_workspace_bytes(plan, 128, M);
+    // a prepared cohort (nplda_cohort_prepare_f32) belongs to the fused path of exactly this shape and top-N
+    if (prepared && (!fused || prepared_bytes < plan.fixed_bytes)) return NPLDA_EINVAL;
+    if (fused) {
+        long long rows_cap = nplda::fused_rows_cap(plan, ws_bytes, M);
+        if (rows_cap > (R + 127) / 128 * 128) rows_cap = (R + 127) / 128 * 128;
+        float* scratch = nplda::fused_scratch_rows(ws, ws_bytes, M);
+        const long long resident = nplda::cohort_fused_resident_blocks();
+        if (resident <= 0) return NPLDA_EINVAL;
+        for (long long r0 = 0; r0 < R; r0 += rows_cap) {
+            const nplda::FusedRequest rq = {
+                {z_rows + r0 * ldz, q_rows + r0, (R - r0 < rows_cap) ? R - r0 : rows_cap, stats + 4 * r0},
+                {z_coh, q_coh, M, ldz, (const unsigned char*)prepared},
+                {P, L.NB, D2},
+                {topn, lowest},
+                {(unsigned char*)ws, rows_cap, r0 == 0, resident, st}};
+            const nplda::FusedResult fr = nplda::cohort_fused_run(plan, rq);
+            if (fr.rc) return fr.rc;
+            const FallbackArgs fb = {rq.rows.z, rq.rows.q, z_coh, q_coh, P, M, ldz, lds, 16 * L.NB, topn, lowest, rl.use_lds,
+                                     fr.fail_rows, fr.nfail, scratch, rq.rows.stats};
+            hipLaunchKernelGGL(cohort_fallback_kernel, dim3(nplda::kFallbackBlocks), dim3(kRowThreads), rl.shmem, st, fb);
+            if (int rc2 = nplda_launch_status()) return rc2;
+        }
+        return NPLDA_OK;
+    }
+
+    // ---- spill path: score matrix in the workspace, then one block per row -----------------------------------------------
+    long long rows_per = (long long)((ws_bytes - kCohortCtlBytes) / row_bytes);
+    if (rows_per > R) rows_per = R;
+    // persistent tile walkers: as many blocks as are resident at once
+    const long long resident = nplda::resident_blocks(cohort_gemm_kernel, 256);
+    if (resident <= 0) return NPLDA_EINVAL;
+    for (long long r0 = 0; r0 < R; r0 += rows_per) {
+        const long long rc = (R - r0 < rows_per) ? R - r0 : rows_per;
+        CohortGemmArgs a;
+        a.zr = z_rows + r0 * ldz; a.qr = q_rows + r0; a.zc = z_coh; a.qc = q_coh;
+        a.P = P; a.R = rc; a.M = M; a.ldz = ldz; a.lds = lds; a.ksteps = L.NB; a.S = (float*)((char*)ws + kCohortCtlBytes);
+        const long long nx = (M + 127) / 128, ny = (rc + 127) / 128;
+        a.nxp = (int)((nx + 7) / 8 < 24 ? (nx + 7) / 8 : 24);
+        a.ny = (int)ny;
+        const long long nsb = (nx + 8LL * a.nxp - 1) / (8LL * a.nxp);
+        if (nx > 0x00ffffffLL || ny > 0x00ffffffLL || (long long)a.nxp * ny * nsb > 0x0fffffffLL) return NPLDA_EINVAL;
+        a.nx = (int)nx;
+        a.nsb = (int)nsb;
+        a.ctr = (unsigned*)ws;
+        long long grid = 8LL * a.nxp * ny;  // at most one block per tile of the busiest XCD
+        if (grid > resident) grid = resident;
+        if (hipMemsetAsync(ws, 0, kCohortCtlBytes, st) != hipSuccess) return NPLDA_EINVAL;
+        hipLaunchKernelGGL(cohort_gemm_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
+        if (int rc2 = nplda_launch_status()) return rc2;
+        hipLaunchKernelGGL(row_stats_kernel, dim3((unsigned)rc), dim3(kRowThreads), rl.shmem, st, (const float*)a.S,
+                           (long long)lds, (long long)M, topn, lowest, rl.use_lds, stats + 4 * r0);
+        if (int rc2 = nplda_launch_status()) return rc2;
+    }
+    return NPLDA_OK;
+}
 
 int nplda_cohort_stats_f32(const float* z_rows, const float* q_rows, int64_t R, const float* z_coh,
                            const float* q_coh, int64_t M, int64_t ldz, const void* packed, int D0, int D1, int D2,
@@ -948,122 +1042,16 @@ int nplda_cohort_stats_prepared_f32(const float* z_rows, const float* q_rows, in
                              ws_bytes, stream, state, state_bytes);
 }
 
-static int cohort_stats_impl(const float* z_rows, const float* q_rows, int64_t R, const float* z_coh,
-                             const float* q_coh, int64_t M, int64_t ldz, const void* packed, int D0, int D1, int D2,
-                             int topn, int select_lowest, double* stats, void* ws, size_t ws_bytes,
-                             nplda_stream_t stream, const void* prepared, size_t prepared_bytes) {
-    if (R < 0 || M < 0 || topn < 1) return NPLDA_EINVAL;
-    if (D0 <= 0 || D1 <= 0 || D2 <= 0 || (D0 % 4) != 0) return NPLDA_EINVAL;
-    if (!nplda_dims_ok(D0, D1, D2)) return NPLDA_EUNSUPPORTED;
-    if (R == 0) return NPLDA_OK;
-    if (M == 0 || M > 0x7ffffff0LL) return NPLDA_EINVAL;
-    const NpldaLayout L = nplda_layout(D0, D1, D2);
-    if (!z_rows || !q_rows || !z_coh || !q_coh || !packed || !stats || !ws) return NPLDA_EINVAL;
-    if (ldz < 16 * L.NB || (ldz % 4) != 0 || !nplda_aligned16(z_rows) || !nplda_aligned16(z_coh) ||
-        !nplda_aligned16(packed) || !nplda_aligned16(ws))
-        return NPLDA_EINVAL;
-    const long long lds = (M + 3) / 4 * 4;
-    const size_t row_bytes = (size_t)lds * sizeof(float);
-    if (ws_bytes < kCohortCtlBytes + row_bytes) return NPLDA_ENOSPC;
-    hipStream_t st = (hipStream_t)stream;
-    const int use_lds = M <= kMaxRowLds ? 1 : 0;
-    const size_t shmem = (use_lds ? (size_t)((M + 3) / 4 * 4) * 4 : 0) + 64 * 4 + (kRowThreads / 64) * 32 + (2 * kListCap + 4 + 8 + kListCap / 2) * 4 + 16;
-    if (use_lds && shmem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)row_stats_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)shmem);
-        if (e != hipSuccess) return (int)e;
-        e = hipFuncSetAttribute((const void*)cohort_fallback_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) return (int)e;
-    }
-
-    // ---- fused path: statistics in the GEMM's epilogue, no score matrix (nplda_cohort_fused.hip) -----------------------
-    // Chosen by the shape (M, top-N) alone, and every row is computed independently of its neighbours, so the result of
-    // a row does not depend on R, on the row's position or on how the workspace chunks the table.
-    const nplda::FusedPlan plan = nplda::cohort_fused_plan(M, topn, 16 * L.NB);
-    // a prepared cohort (nplda_cohort_prepare_f32) belongs to the fused path of exactly this shape and top-N
-    if (prepared && (!plan.eligible || prepared_bytes < plan.fixed_bytes || ws_bytes < fused_workspace_bytes(plan, 128, M)))
-        return NPLDA_EINVAL;
-    if (plan.eligible && ws_bytes >= fused_workspace_bytes(plan, 128, M)) {
-        const size_t scratch_bytes = (size_t)kFallbackBlocks * lds * sizeof(float);
-        long long rows_cap = (long long)((ws_bytes - plan.fixed_bytes - scratch_bytes - 256) / plan.row_bytes) / 128 * 128;
-        if (rows_cap > plan.max_rows) rows_cap = plan.max_rows;
-        if (rows_cap > (R + 127) / 128 * 128) rows_cap = (R + 127) / 128 * 128;
-        float* scratch = (float*)((char*)ws + (ws_bytes - scratch_bytes) / 256 * 256);
-        const long long resident = nplda::cohort_fused_resident_blocks();
-        if (resident <= 0) return NPLDA_EINVAL;
-        for (long long r0 = 0; r0 < R; r0 += rows_cap) {
-            const long long rc = (R - r0 < rows_cap) ? R - r0 : rows_cap;
-            unsigned* fail_rows = nullptr;
-            unsigned* nfail = nullptr;
-            if (int rc2 = nplda::cohort_fused_run(plan, z_rows + r0 * ldz, q_rows + r0, rc, z_coh, q_coh, M, ldz,
-                                                  (const float*)packed + L.oP, L.NB, topn, select_lowest ? 1 : 0,
-                                                  stats + 4 * r0, (unsigned char*)ws, rows_cap, r0 == 0, &fail_rows,
-                                                  &nfail, resident, st, (const unsigned char*)prepared, D2))
-                return rc2;
-            FallbackArgs fb;
-            fb.zr = z_rows + r0 * ldz; fb.qr = q_rows + r0; fb.zc = z_coh; fb.qc = q_coh; fb.P = (const float*)packed + L.oP;
-            fb.M = M; fb.ldz = ldz; fb.lds = lds; fb.kp = 16 * L.NB; fb.topn = topn; fb.lowest = select_lowest ? 1 : 0;
-            fb.use_lds = use_lds; fb.fail_rows = fail_rows; fb.nfail = nfail; fb.scratch = scratch; fb.stats = stats + 4 * r0;
-            hipLaunchKernelGGL(cohort_fallback_kernel, dim3(kFallbackBlocks), dim3(kRowThreads), shmem, st, fb);
-            if (int rc2 = nplda_launch_status()) return rc2;
-        }
-        return NPLDA_OK;
-    }
-
-    // ---- spill path: score matrix in the workspace, then one block per row -----------------------------------------------
-    long long rows_per = (long long)((ws_bytes - kCohortCtlBytes) / row_bytes);
-    if (rows_per > R) rows_per = R;
-    // persistent tile walkers: as many blocks as are resident at once, a multiple of 8 so that a block keeps its XCD
-    long long resident = 0;
-    {
-        int dev = 0, cus = 0, per_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cohort_gemm_kernel, 256, 0) != hipSuccess)
-            return NPLDA_EINVAL;
-        resident = (long long)cus * per_cu / 8 * 8;
-        if (resident < 8) resident = 8;
-    }
-    for (long long r0 = 0; r0 < R; r0 += rows_per) {
-        const long long rc = (R - r0 < rows_per) ? R - r0 : rows_per;
-        CohortGemmArgs a;
-        a.zr = z_rows + r0 * ldz; a.qr = q_rows + r0; a.zc = z_coh; a.qc = q_coh;
-        a.P = (const float*)packed + L.oP; a.R = rc; a.M = M; a.ldz = ldz; a.lds = lds; a.ksteps = L.NB; a.S = (float*)((char*)ws + kCohortCtlBytes);
-        const long long nx = (M + 127) / 128, ny = (rc + 127) / 128;
-        a.nxp = (int)((nx + 7) / 8 < 24 ? (nx + 7) / 8 : 24);
-        a.ny = (int)ny;
-        const long long nsb = (nx + 8LL * a.nxp - 1) / (8LL * a.nxp);
-        if (nx > 0x00ffffffLL || ny > 0x00ffffffLL || (long long)a.nxp * ny * nsb > 0x0fffffffLL) return NPLDA_EINVAL;
-        a.nx = (int)nx;
-        a.nsb = (int)nsb;
-        a.ctr = (unsigned*)ws;
-        long long grid = 8LL * a.nxp * ny;  // at most one block per tile of the busiest XCD
-        if (grid > resident) grid = resident;
-        if (hipMemsetAsync(ws, 0, kCohortCtlBytes, st) != hipSuccess) return NPLDA_EINVAL;
-        hipLaunchKernelGGL(cohort_gemm_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
-        if (int rc2 = nplda_launch_status()) return rc2;
-        hipLaunchKernelGGL(row_stats_kernel, dim3((unsigned)rc), dim3(kRowThreads), shmem, st, (const float*)((const char*)ws + kCohortCtlBytes),
-                           (long long)lds, (long long)M, topn, select_lowest ? 1 : 0, use_lds, stats + 4 * r0);
-        if (int rc2 = nplda_launch_status()) return rc2;
-    }
-    return NPLDA_OK;
-}
-
 int nplda_row_stats_f32(const float* S, int64_t lds, int64_t R, int64_t M, int topn, int select_lowest, double* stats,
                         nplda_stream_t stream) {
     if (R < 0 || M < 0 || topn < 1) return NPLDA_EINVAL;
     if (R == 0) return NPLDA_OK;
     if (M == 0 || !S || !stats || lds < M) return NPLDA_EINVAL;
-    const int use_lds = M <= kMaxRowLds ? 1 : 0;
-    const size_t shmem = (use_lds ? (size_t)((M + 3) / 4 * 4) * 4 : 0) + 64 * 4 + (kRowThreads / 64) * 32 + (2 * kListCap + 4 + 8 + kListCap / 2) * 4 + 16;
-    if (use_lds && shmem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)row_stats_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)shmem);
-        if (e != hipSuccess) return (int)e;
-    }
+    const RowKernelLds rl = row_kernel_lds(M);
+    if (rl.rc) return rl.rc;
     if (R > 0x7fffffffLL || M > 0x7ffffff0LL) return NPLDA_EINVAL;  // 32-bit group indices inside the kernel
-    hipLaunchKernelGGL(row_stats_kernel, dim3((unsigned)R), dim3(kRowThreads), shmem, (hipStream_t)stream, S,
-                       (long long)lds, (long long)M, topn, select_lowest ? 1 : 0, use_lds, stats);
+    hipLaunchKernelGGL(row_stats_kernel, dim3((unsigned)R), dim3(kRowThreads), rl.shmem, (hipStream_t)stream, S,
+                       (long long)lds, (long long)M, topn, select_lowest ? 1 : 0, rl.use_lds, stats);
     return nplda_launch_status();
 }
 

@@ -32,11 +32,6 @@
 #include "nplda_cohort_fused.h"
 #include "nplda_cohort_qz.h"
 
-namespace nplda {
-int gram_slabs_launch(const float* Z, long long ldz, long long rows, int Mp, int ksplit, float* slab, float* ext,
-                      const QzArgs* qz, hipStream_t st);
-}  // namespace nplda
-
 #ifdef NPLDA_COHORT_ABLATE
 static unsigned long long* g_cf_stamps = nullptr;
 extern "C" __attribute__((visibility("default"))) int nplda_cohort_debug_stamps(unsigned long long* host_out) {
@@ -1088,7 +1083,6 @@ inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 namespace nplda {
 
-// inverse normal CDF (Abramowitz & Stegun 26.2.23), host side
 // Floats of padding behind a row's list region.  Without it two rows' regions are nsub * ksub * 4 B = a power of two
 // apart (32 KB at cfg3) and the lines a block's 256 rows are appending to compete for the same few L2 sets: they were
 // written back half filled and re-opened — 436 MB of L2 write-backs per cfg3 call for 94 MB of candidates.  An odd number of
@@ -1113,6 +1107,84 @@ static int fused_row_pad() {
     return pad;
 }
 
+// ---- workspace map ------------------------------------------------------------------------------------------------
+// THE description of a fused workspace (ws, ws_bytes): every size the queries answer and every address a kernel is handed
+// comes from the two walks and the three functions below.
+//   ws                                    fixed part (fused_fixed): the control block — work-item counters, and the fail
+//                                         count at word kFusedFailWord — then the pre-pass's scratch and its results.
+//                                         A CohortState (cohort_fused_prepare) is this part alone.
+//   ws + fused_fixed().bytes              per-row arrays (fused_row_arrays), carved for rows_cap rows
+//   behind them                           kRowSlack bytes, and whatever a larger ws_bytes leaves over
+//   ws + (ws_bytes - scratch) / 256 * 256 kFallbackBlocks scratch score rows (fused_scratch_rows); rounding the start down
+//                                         costs up to 255 bytes: the trailing 256 of fused_workspace_bytes
+// A walk takes its pieces in order, each rounded up to 256 bytes; with a null base it only counts (`off`).
+struct Carve {
+    unsigned char* base; size_t off;
+    template <class T> T* take(size_t bytes) {
+        T* at = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += align256(bytes);
+        return at;
+    }
+};
+struct FusedFixed {
+    unsigned* ctl; float* slab; float* ext; float* qz; double* qz64; double* vec64; float* frag; float* vec;
+    unsigned char* img;   // the cohort's split image: ceil(M / 64) tiles of split_tile_bytes(Mp) (cohort_split_kernel)
+    size_t bytes;
+};
+static FusedFixed fused_fixed(unsigned char* ws, int Mp, long long M) {
+    Carve c = {ws, 0};
+    const size_t kb = (size_t)Mp / 16;
+    FusedFixed f;
+    f.ctl = c.take<unsigned>(256);
+    f.slab = c.take<float>((size_t)kGramSplit * Mp * Mp * 4);
+    f.ext = c.take<float>((size_t)kGramSplit * 4 * Mp * 4);
+    f.qz = c.take<float>((size_t)kQzBlocks * (Mp + 2) * 4);
+    f.qz64 = c.take<double>((size_t)kQzBlocks * (Mp + 1) * 8);
+    f.vec64 = c.take<double>((size_t)(Mp + 1) * 8);
+    f.frag = c.take<float>(kb * kb * 256 * 4);
+    f.vec = c.take<float>((size_t)(2 * Mp + 2) * 4);
+    f.img = c.take<unsigned char>((size_t)((M + 63) / 64) * split_tile_bytes(Mp));
+    f.bytes = c.off;
+    return f;
+}
+// floats of one row's candidate lists
+static long long fused_lrow(const FusedPlan& p) { return (long long)p.nsub * p.ksub + fused_row_pad(); }
+struct FusedRowArrays {
+    double* part; double* mean64; float* lists; unsigned* counts; float* crow; float* trow; unsigned* fail_rows;
+    size_t bytes;
+};
+static FusedRowArrays fused_row_arrays(unsigned char* base, const FusedPlan& p, long long rows) {
+    Carve c = {base, 0};
+    const size_t n = (size_t)rows;
+    FusedRowArrays a;
+    a.part = c.take<double>(n * (p.nsub / 4) * 8);
+    a.mean64 = c.take<double>(n * 8);
+    a.lists = c.take<float>(n * fused_lrow(p) * 4);
+    a.counts = c.take<unsigned>(n * p.nsub * 4);
+    a.crow = c.take<float>(n * 4);
+    a.trow = c.take<float>(n * 4);
+    a.fail_rows = c.take<unsigned>(n * 4);
+    a.bytes = c.off;
+    return a;
+}
+// Rows come in multiples of 128 and every array holds a multiple of 4 bytes per row, so each is a multiple of 512 bytes:
+// the walk loses nothing to alignment and fused_row_arrays(rows).bytes == rows * FusedPlan::row_bytes.  The 8 x 256 bytes
+// that FusedPlan::fixed_bytes has always carried for that alignment stay in it (the size queries are part of the ABI).
+constexpr size_t kRowSlack = 8 * 256;
+
+static size_t fused_scratch_bytes(long long M) { return (size_t)kFallbackBlocks * (size_t)((M + 3) / 4 * 4) * sizeof(float); }
+size_t fused_workspace_bytes(const FusedPlan& p, long long rows, long long M) {
+    return p.fixed_bytes + (size_t)rows * p.row_bytes + fused_scratch_bytes(M) + 256;
+}
+long long fused_rows_cap(const FusedPlan& p, size_t ws_bytes, long long M) {
+    const long long rows = (long long)((ws_bytes - fused_workspace_bytes(p, 0, M)) / p.row_bytes) / 128 * 128;
+    return rows < p.max_rows ? rows : p.max_rows;
+}
+float* fused_scratch_rows(void* ws, size_t ws_bytes, long long M) {
+    return (float*)((char*)ws + (ws_bytes - fused_scratch_bytes(M)) / 256 * 256);
+}
+
+// inverse normal CDF (Abramowitz & Stegun 26.2.23), host side
 static float host_normcdfinv(double p) {
     const bool lower = p < 0.5;
     const double pp = lower ? p : 1.0 - p;
@@ -1180,50 +1252,22 @@ FusedPlan cohort_fused_plan(long long M, int topn, int Mp) {
     }
     p.zhi = host_normcdfinv(f);
     p.fhi = (float)f;
-    const size_t kb = (size_t)Mp / 16;
-    p.fixed_bytes = 256 + align256((size_t)kGramSplit * Mp * Mp * 4) + align256((size_t)kGramSplit * 4 * Mp * 4) +
-                    align256((size_t)kQzBlocks * (Mp + 2) * 4) + align256((size_t)kQzBlocks * (Mp + 1) * 8) +
-                    align256((size_t)(Mp + 1) * 8) + align256(kb * kb * 256 * 4) +
-                    align256((size_t)(2 * Mp + 2) * 4) + 8 * 256 +  // + the alignment slack of the per-row arrays
-                    align256((size_t)((M + 63) / 64) * split_tile_bytes(Mp));  // the cohort's split image (cohort_split_kernel)
-    const long long lrow = (long long)p.nsub * p.ksub + fused_row_pad();
-    p.max_rows = ((1LL << 30) / lrow) / 256 * 256;  // 32-bit BYTE offsets into the lists
-    p.row_bytes = 8 + 8 + (size_t)lrow * 4 + (size_t)p.nsub * 4 + (size_t)(p.nsub / 4) * 8 + 4;
+    p.max_rows = ((1LL << 30) / fused_lrow(p)) / 256 * 256;  // 32-bit BYTE offsets into the lists
+    p.fixed_bytes = fused_fixed(nullptr, Mp, M).bytes + kRowSlack;
+    p.row_bytes = fused_row_arrays(nullptr, p, 128).bytes / 128;
     p.eligible = true;
     return p;
 }
 
-// Runs the fused path on rows [0, R) (R <= the rows the workspace was planned for).  `fail_rows` / `nfail` (device)
-// receive the rows that need the general path; the caller runs cohort_fallback_kernel on them.
-// the fixed part of a workspace (FusedPlan::fixed_bytes): control block, the pre-pass's scratch and its results
-struct FusedFixed {
-    unsigned* ctl; float* slab; float* ext; float* qz; double* qz64; double* vec64; float* frag; float* vec;
-    unsigned char* img;   // the cohort's split image: ceil(M / 64) tiles of split_tile_bytes(Mp)
-    unsigned char* end;
-};
-static FusedFixed fused_fixed(unsigned char* ws, int Mp, long long M) {
-    FusedFixed f;
-    unsigned char* q = ws;
-    f.ctl = reinterpret_cast<unsigned*>(q); q += 256;
-    f.slab = reinterpret_cast<float*>(q); q += align256((size_t)kGramSplit * Mp * Mp * 4);
-    f.ext = reinterpret_cast<float*>(q); q += align256((size_t)kGramSplit * 4 * Mp * 4);
-    f.qz = reinterpret_cast<float*>(q); q += align256((size_t)kQzBlocks * (Mp + 2) * 4);
-    f.qz64 = reinterpret_cast<double*>(q); q += align256((size_t)kQzBlocks * (Mp + 1) * 8);
-    f.vec64 = reinterpret_cast<double*>(q); q += align256((size_t)(Mp + 1) * 8);
-    f.frag = reinterpret_cast<float*>(q); q += align256((size_t)(Mp / 16) * (Mp / 16) * 256 * 4);
-    f.vec = reinterpret_cast<float*>(q); q += align256((size_t)(2 * Mp + 2) * 4);
-    f.img = q; q += align256((size_t)((M + 63) / 64) * split_tile_bytes(Mp));
-    f.end = q;
-    return f;
-}
-
 // cohort moments: second and first moments of the cohort in ONE launch (the first-moment blocks ride along as extra work
 // items), then the centred covariance folded with 2 P into a fragment image
-static int fused_prepass(const FusedFixed& F, const float* z_coh, const float* q_coh, long long M, long long ldz, const float* P,
-                         int Mp, hipStream_t st) {
-    const QzArgs qa = {z_coh, q_coh, M, ldz, Mp, kQzBlocks, F.qz, F.qz64};
+static int fused_prepass(const FusedFixed& F, const CohortTable& coh, const CohortModel& net, hipStream_t st) {
+    const float* z_coh = coh.z;
+    const long long M = coh.M, ldz = coh.ldz;
+    const int Mp = 16 * net.ksteps;
+    const QzArgs qa = {z_coh, coh.q, M, ldz, Mp, kQzBlocks, F.qz, F.qz64};
     if (int rc = gram_slabs_launch(z_coh, ldz, M, Mp, kGramSplit, F.slab, F.ext, &qa, st)) return rc;
-    PrepArgs pa = {F.slab, F.ext, F.qz, F.qz64, P, kGramSplit, Mp, M, F.frag, F.vec, F.vec64, F.ctl};
+    PrepArgs pa = {F.slab, F.ext, F.qz, F.qz64, net.P, kGramSplit, Mp, M, F.frag, F.vec, F.vec64, F.ctl};
     // ksplit actually used by gram_slabs_launch: rows per split rounded up -> some trailing slabs may be unwritten
     {
         long long rps = (M + kGramSplit - 1) / kGramSplit;
@@ -1240,49 +1284,51 @@ static int fused_prepass(const FusedFixed& F, const float* z_coh, const float* q
     return nplda_launch_status();
 }
 
-int cohort_fused_prepare(const FusedPlan& p, const float* z_coh, const float* q_coh, long long M, long long ldz, const float* P,
-                         int ksteps, unsigned char* state, hipStream_t st) {
-    if (!p.eligible) return NPLDA_EUNSUPPORTED;
-    return fused_prepass(fused_fixed(state, 16 * ksteps, M), z_coh, q_coh, M, ldz, P, 16 * ksteps, st);
+// cohort_fused2_kernel<LOWEST, NB, RGW, KT, NW, SPLIT> for one (NB, KT, SPLIT): 256-row tiles (RGW = 2), 128-row tiles, or —
+// the fp32-input form at NB = 10 / 11 only — the 16-wave block
+struct FusedLaunch { bool nw16, half_tiles, lowest; unsigned grid; hipStream_t st; const FusedArgs* fa; };
+template <int NB, int RGW, int KT, int NW, bool SPLIT>
+static void launch_fused2_form(const FusedLaunch& l) {
+    if (l.lowest) hipLaunchKernelGGL((cohort_fused2_kernel<true, NB, RGW, KT, NW, SPLIT>), dim3(l.grid), dim3(64 * NW), 0, l.st, *l.fa);
+    else hipLaunchKernelGGL((cohort_fused2_kernel<false, NB, RGW, KT, NW, SPLIT>), dim3(l.grid), dim3(64 * NW), 0, l.st, *l.fa);
+}
+template <int NB, int KT, bool SPLIT = false>
+static void launch_fused2(const FusedLaunch& l) {
+    if (l.nw16 && !SPLIT) {
+        if constexpr (!SPLIT && (NB == 10 || NB == 11)) launch_fused2_form<NB, 1, KT, 16, false>(l);
+    } else if (l.half_tiles) launch_fused2_form<NB, 1, KT, 8, SPLIT>(l);
+    else launch_fused2_form<NB, 2, KT, 8, SPLIT>(l);
 }
 
-int cohort_fused_run(const FusedPlan& p, const float* z_rows, const float* q_rows, long long R, const float* z_coh,
-                     const float* q_coh, long long M, long long ldz, const float* P, int ksteps, int topn, int lowest,
-                     double* stats, unsigned char* ws, long long rows_cap, bool prepass, unsigned** fail_rows_out,
-                     unsigned** nfail_out, long long resident, hipStream_t st, const unsigned char* prepared, int D2) {
-    const int Mp = 16 * ksteps;
-    const FusedFixed F = fused_fixed(ws, Mp, M);
+int cohort_fused_prepare(const FusedPlan& p, const CohortTable& coh, const CohortModel& net, unsigned char* state, hipStream_t st) {
+    if (!p.eligible) return NPLDA_EUNSUPPORTED;
+    return fused_prepass(fused_fixed(state, 16 * net.ksteps, coh.M), coh, net, st);
+}
+
+FusedResult cohort_fused_run(const FusedPlan& p, const FusedRequest& rq) {
+    const float* z_rows = rq.rows.z; const float* q_rows = rq.rows.q;
+    const long long R = rq.rows.R, M = rq.coh.M, ldz = rq.coh.ldz, resident = rq.exec.resident;
+    const int ksteps = rq.net.ksteps, lowest = rq.sel.lowest, Mp = 16 * ksteps;
+    hipStream_t st = rq.exec.st;
+    const FusedFixed F = fused_fixed(rq.exec.ws, Mp, M);
     unsigned* ctl = F.ctl;
-    unsigned char* q = F.end;
     // (a prepared cohort: its covariance image and moment vectors are read where cohort_fused_prepare left them)
-    const FusedFixed FP = prepared ? fused_fixed(const_cast<unsigned char*>(prepared), Mp, M) : F;
-    const double* vec64 = FP.vec64;
-    const float* frag = FP.frag;
-    const float* vec = FP.vec;
-    if (prepared) prepass = false;
-    // per-row arrays, sized for rows_cap rows
-    double* part = reinterpret_cast<double*>(q); q += align256((size_t)rows_cap * (p.nsub / 4) * 8);
-    double* mean64 = reinterpret_cast<double*>(q); q += align256((size_t)rows_cap * 8);
-    const int lrow = p.nsub * p.ksub + fused_row_pad();
-    float* lists = reinterpret_cast<float*>(q); q += align256((size_t)rows_cap * lrow * 4);
-    unsigned* counts = reinterpret_cast<unsigned*>(q); q += align256((size_t)rows_cap * p.nsub * 4);
-    float* crow = reinterpret_cast<float*>(q); q += align256((size_t)rows_cap * 4);
-    float* trow = reinterpret_cast<float*>(q); q += align256((size_t)rows_cap * 4);
-    unsigned* fail_rows = reinterpret_cast<unsigned*>(q);
-    *fail_rows_out = fail_rows;
-    *nfail_out = ctl + 8;
+    const FusedFixed FP = rq.coh.prepared ? fused_fixed(const_cast<unsigned char*>(rq.coh.prepared), Mp, M) : F;
+    const bool prepass = rq.exec.prepass && !rq.coh.prepared;
+    const FusedRowArrays A = fused_row_arrays(rq.exec.ws + F.bytes, p, rq.exec.rows_cap);
+    const int lrow = (int)fused_lrow(p);
 
     // (the control block — work-item counters, fail count — is zeroed by the pre-pass, or, with a prepared cohort, by the
     // row-threshold kernel below: a hipMemsetAsync in front cost a launch, and as a memset NODE of a captured graph it let a
     // replayed AS-norm step fault — tools/exp_cfg3_graph.py, round 6)
     if (prepass) {  // cohort moments: once per call, the cohort does not change between row chunks
-        if (int rc = fused_prepass(F, z_coh, q_coh, M, ldz, P, Mp, st)) return rc;
+        if (int rc = fused_prepass(F, rq.coh, rq.net, st)) return {rc};
     }
     {   // row means and thresholds
         // rows per block: 128, or fewer (down to 32) when 128-row tiles would leave most CUs without a block
         int wpt = 8;
         while (wpt > 2 && (R + 16 * wpt - 1) / (16 * wpt) < resident / 2) wpt >>= 1;
-        RowThrArgs ra = {z_rows, q_rows, R, ldz, frag, vec, vec64, p.zhi, lowest ? 1.0f : -1.0f, crow, trow, mean64,
+        RowThrArgs ra = {z_rows, q_rows, R, ldz, FP.frag, FP.vec, FP.vec64, p.zhi, lowest ? 1.0f : -1.0f, A.crow, A.trow, A.mean64,
                          (int)((R + 16 * wpt - 1) / (16 * wpt)), wpt, prepass ? nullptr : ctl};
         const unsigned grid = (unsigned)(ra.ntiles < resident ? ra.ntiles : resident);
         const size_t shm = (size_t)ksteps * (ksteps + 1) / 2 * 1024;
@@ -1290,7 +1336,7 @@ int cohort_fused_run(const FusedPlan& p, const float* z_rows, const float* q_row
     {                                                                                                                 \
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&cohort_rowthr_kernel<NBV>),                             \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)                  \
-            return NPLDA_EINVAL;                                                                                      \
+            return {NPLDA_EINVAL};                                                                                    \
         hipLaunchKernelGGL(cohort_rowthr_kernel<NBV>, dim3(grid), dim3(512), shm, st, ra);                            \
     }
         switch (ksteps) {
@@ -1300,14 +1346,14 @@ int cohort_fused_run(const FusedPlan& p, const float* z_rows, const float* q_row
             case 10: NPLDA_LAUNCH(10); break;
             case 11: NPLDA_LAUNCH(11); break;
             case 12: NPLDA_LAUNCH(12); break;
-            default: return NPLDA_EUNSUPPORTED;
+            default: return {NPLDA_EUNSUPPORTED};
         }
 #undef NPLDA_LAUNCH
-        if (int rc = nplda_launch_status()) return rc;
+        if (int rc = nplda_launch_status()) return {rc};
     }
 
     FusedArgs fa = {};
-    fa.zr = z_rows; fa.qr = q_rows; fa.zc = z_coh; fa.qc = q_coh; fa.P = P;
+    fa.zr = z_rows; fa.qr = q_rows; fa.zc = rq.coh.z; fa.qc = rq.coh.q; fa.P = rq.net.P;
     fa.zc3 = FP.img;
     // Row tiles of 256 rows — or of 128 when the call has so few rows that 256-row items would leave most CUs idle in the
     // last round (fewer than three items per resident block: an 8-way row shard of cfg3 is 11 tiles x 32 list bands for
@@ -1319,7 +1365,7 @@ int cohort_fused_run(const FusedPlan& p, const float* z_rows, const float* q_row
     if (const char* e = getenv("NPLDA_COHORT_HALF")) half_tiles = p.q > 1 && e[0] == '1';   // (A/B runs: force 128- / 256-row tiles)
     const int rpb = half_tiles ? 128 : 256;
     fa.R = R; fa.M = M; fa.ldz = ldz; fa.ksteps = ksteps; fa.nbands = p.nbands; fa.ny = (int)((R + rpb - 1) / rpb); fa.nx = p.nx;
-    fa.ctr = ctl; fa.crow = crow; fa.trow = trow; fa.lists = lists; fa.counts = counts; fa.part = part;
+    fa.ctr = ctl; fa.crow = A.crow; fa.trow = A.trow; fa.lists = A.lists; fa.counts = A.counts; fa.part = A.part;
     fa.nsub = p.nsub; fa.q = p.q; fa.ksub = p.ksub; fa.lrow = lrow;
     // (the split form: 2 = the MFMA loop at priority 0, everything else of a tile at 3 — with a bf16 MFMA stream at priority 0 the
     // partner's VALU instructions at priority 3 issue beside it at no cost to the stream, which the fp32-input MFMAs do not allow:
@@ -1346,65 +1392,38 @@ int cohort_fused_run(const FusedPlan& p, const float* z_rows, const float* q_row
     }
     // k4-steps of the last k16-block (cohort_fused2_kernel, KT): the instantiated short forms are D2 in 145 .. 152 at NB = 10
     // (KT = 2: the reference's 150) and D2 in 169 .. 172 at NB = 11 (KT = 3: the shipped 170)
-    const int tail = D2 > 0 ? D2 - 16 * (ksteps - 1) : 16;
+    const int tail = rq.net.D2 - 16 * (ksteps - 1);
     const int kt = (ksteps == 10 && tail >= 1 && tail <= 8) ? 2 : ((ksteps == 11 && tail >= 9 && tail <= 12) ? 3 : 4);
     static const bool no_kt = getenv("NPLDA_COHORT_NO_KTAIL") != nullptr && getenv("NPLDA_COHORT_NO_KTAIL")[0] == '1';  // A/B only
     // four waves per SIMD (NW = 16: a wave owns ONE 16-row group, the block the same 256 rows; 128 VGPRs per wave): while one
     // wave's MFMA loop has the matrix pipe, three partners — not one — work through their epilogues in the issue slots it leaves
     static const int nw_env = getenv("NPLDA_COHORT_NW") ? atoi(getenv("NPLDA_COHORT_NW")) : 8;
     const bool nw16 = nw_env == 16 && !half_tiles && (ksteps == 10 || ksteps == 11);
-#define NPLDA_LAUNCH_KT(NBV, KTV)                                                                                                   \
-    if (nw16) {                                                                                                                     \
-        if constexpr (NBV == 10 || NBV == 11) {                                                                                     \
-            if (lowest) hipLaunchKernelGGL((cohort_fused2_kernel<true, NBV, 1, KTV, 16>), dim3((unsigned)grid), dim3(1024), 0, st, fa);  \
-            else hipLaunchKernelGGL((cohort_fused2_kernel<false, NBV, 1, KTV, 16>), dim3((unsigned)grid), dim3(1024), 0, st, fa);        \
-        }                                                                                                                           \
-    } else if (half_tiles) {                                                                                                               \
-        if (lowest) hipLaunchKernelGGL((cohort_fused2_kernel<true, NBV, 1, KTV>), dim3((unsigned)grid), dim3(512), 0, st, fa);       \
-        else hipLaunchKernelGGL((cohort_fused2_kernel<false, NBV, 1, KTV>), dim3((unsigned)grid), dim3(512), 0, st, fa);             \
-    } else if (lowest) hipLaunchKernelGGL((cohort_fused2_kernel<true, NBV, 2, KTV>), dim3((unsigned)grid), dim3(512), 0, st, fa);    \
-    else hipLaunchKernelGGL((cohort_fused2_kernel<false, NBV, 2, KTV>), dim3((unsigned)grid), dim3(512), 0, st, fa)
-#define NPLDA_LAUNCH(NBV) NPLDA_LAUNCH_KT(NBV, 4)
-#define NPLDA_LAUNCH_SPLIT(NBV)                                                                                                      \
-    if (half_tiles) {                                                                                                                \
-        if (lowest) hipLaunchKernelGGL((cohort_fused2_kernel<true, NBV, 1, 4, 8, true>), dim3((unsigned)grid), dim3(512), 0, st, fa);  \
-        else hipLaunchKernelGGL((cohort_fused2_kernel<false, NBV, 1, 4, 8, true>), dim3((unsigned)grid), dim3(512), 0, st, fa);        \
-    } else if (lowest) hipLaunchKernelGGL((cohort_fused2_kernel<true, NBV, 2, 4, 8, true>), dim3((unsigned)grid), dim3(512), 0, st, fa); \
-    else hipLaunchKernelGGL((cohort_fused2_kernel<false, NBV, 2, 4, 8, true>), dim3((unsigned)grid), dim3(512), 0, st, fa)
+    const FusedLaunch fl = {nw16, half_tiles, lowest != 0, (unsigned)grid, st, &fa};
     if (split_selected(ksteps)) {
-        if (ksteps == 10) { NPLDA_LAUNCH_SPLIT(10); } else { NPLDA_LAUNCH_SPLIT(11); }
+        if (ksteps == 10) launch_fused2<10, 4, true>(fl); else launch_fused2<11, 4, true>(fl);
     } else
     switch (ksteps) {
-        case 2: NPLDA_LAUNCH(2); break;
-        case 4: NPLDA_LAUNCH(4); break;
-        case 8: NPLDA_LAUNCH(8); break;
+        case 2: launch_fused2<2, 4>(fl); break;
+        case 4: launch_fused2<4, 4>(fl); break;
+        case 8: launch_fused2<8, 4>(fl); break;
         case 10:
-            if (kt == 2 && !no_kt) { NPLDA_LAUNCH_KT(10, 2); } else { NPLDA_LAUNCH(10); }
+            if (kt == 2 && !no_kt) launch_fused2<10, 2>(fl); else launch_fused2<10, 4>(fl);
             break;
         case 11:
-            if (kt == 3 && !no_kt) { NPLDA_LAUNCH_KT(11, 3); } else { NPLDA_LAUNCH(11); }
+            if (kt == 3 && !no_kt) launch_fused2<11, 3>(fl); else launch_fused2<11, 4>(fl);
             break;
-        case 12: NPLDA_LAUNCH(12); break;
-        default: return NPLDA_EUNSUPPORTED;
+        case 12: launch_fused2<12, 4>(fl); break;
+        default: return {NPLDA_EUNSUPPORTED};
     }
-#undef NPLDA_LAUNCH
-#undef NPLDA_LAUNCH_KT
-#undef NPLDA_LAUNCH_SPLIT
-    if (int rc = nplda_launch_status()) return rc;
-    FinishArgs fi = {lists, counts, part, crow, mean64, R, M, trow, p.zhi, p.fhi, p.nsub, p.nsub, topn, lowest, p.ksub, p.cap, lrow, ctl + 8,
-                     fail_rows, stats};
+    if (int rc = nplda_launch_status()) return {rc};
+    unsigned* nfail = ctl + kFusedFailWord;
+    FinishArgs fi = {A.lists, A.counts, A.part, A.crow, A.mean64, R, M, A.trow, p.zhi, p.fhi, p.nsub, p.nsub, rq.sel.topn, lowest, p.ksub, p.cap,
+                     lrow, nfail, A.fail_rows, rq.rows.stats};
     hipLaunchKernelGGL(cohort_finish_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), (size_t)p.cap * 16, st, fi);
-    return nplda_launch_status();
+    return {nplda_launch_status(), A.fail_rows, nfail};
 }
 
-long long cohort_fused_resident_blocks() {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cohort_fused2_kernel<true, 12, 2>, 512, 0) != hipSuccess)
-        return 0;
-    long long r = (long long)cus * per_cu / 8 * 8;
-    return r < 8 ? 8 : r;
-}
+long long cohort_fused_resident_blocks() { return resident_blocks(cohort_fused2_kernel<true, 12, 2>, 512); }
 
 }  // namespace nplda

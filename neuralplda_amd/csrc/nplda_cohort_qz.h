@@ -17,6 +17,11 @@ struct QzArgs {
                        // from these (mean_r = q_r + mean q + 2 (P z_r) . mean z)
 };
 
+// The cohort's Gram matrix with these blocks riding along: defined beside wgrad_kernel (nplda_backward.hip), called by the
+// fused path's pre-pass (nplda_cohort_fused.hip).
+int gram_slabs_launch(const float* Z, long long ldz, long long rows, int Mp, int ksplit, float* slab, float* ext,
+                      const QzArgs* qz, hipStream_t st);
+
 constexpr size_t kQzSmemBytes = 4 * (NPLDA_MAX_DIM + 2) * sizeof(float) + 4 * (NPLDA_MAX_DIM + 1) * sizeof(double);
 
 // block `b` of a.nblocks (256 threads); smem: kQzSmemBytes, 8-byte aligned

@@ -1140,6 +1140,7 @@ def cohort_stats(z_rows, q_rows, z_coh, q_coh, packed, topn=500, select="lowest"
     _lib.check(code, "nplda_cohort_stats_prepared_f32" if use_prep else "nplda_cohort_stats_f32")
     if return_fallback_rows:
         fused = lib.nplda_cohort_fused_min_workspace_bytes(M, int(topn), packed.D1, packed.D2)
+        # word 8 of a fused workspace: the fail count (kFusedFailWord, csrc/nplda_cohort_fused.h)
         return stats, (int(ws.view(torch.int32)[8].item()) if fused and wsb >= fused else None)
     return stats
 
