@@ -632,6 +632,35 @@ int nplda_pav_apply_f32(const float* scores, int64_t N, const double* lo, const 
 int nplda_pav_apply_f64(const double* scores, int64_t N, const double* lo, const double* hi, const double* llr, int64_t nb,
                         void* out, int out_f64, nplda_stream_t stream);
 
+/* ---- group bootstrap of EER, min cost, actual cost and Cllr (csrc/nplda_bootstrap.hip) -------------------------------- */
+
+/* B bootstrap replicates of the detection metrics over ONE sorted trial list (design/k20_bootstrap.md).  scores, target:
+ * N fp32 (target as above; a trial with a NaN score is excluded); g1, g2: N int32 group ids of the two trial sides in
+ * [0, G1) and [0, G2); g2 = NULL with G2 = 0 resamples side 1 alone.  Replicate b = 1 .. B draws G1 (and G2) groups with
+ * replacement from the counter-based generator of the design note (splitmix64 finaliser, keyed by seed, b and the side);
+ * a trial weighs the product of the draw counts of its two groups.  Row 0 is the point estimate (all weights 1).
+ * out: (B + 1) x ncol DEVICE doubles, ncol = K + 1 + (is_llr ? K + 1 : 0): min cost at betas[0 .. K) (every distinct
+ * score and +inf as threshold, target iff s >= th), the interpolated EER of nplda_detcost_sweep_f32's exact mode, then
+ * with is_llr P_miss + beta P_fa at the threshold log(beta) and Cllr in bits.  totals: (B + 1) x 2 DEVICE int64, the
+ * weighted N_tgt, N_non.  A replicate with an empty class has NaN in every column; nothing else produces a NaN.
+ * betas: K HOST doubles.  After the call the first 16 bytes of the workspace hold two DEVICE int64 flags: the number of
+ * trials whose group id was out of range (such a trial is excluded, never used as an index) and the number of draw
+ * counts above 255 (stored saturated: the result is then not the bootstrap's).
+ * Everything is enqueued on `stream`; nothing is read back, the number of launches depends on (N, B, G1, G2) only and
+ * the result is bitwise repeatable (integer atomics and counts, fixed-order fp64 sums).
+ * Limits: 2 <= N < 2^31, 1 <= G1 <= 2^20, G2 <= 2^20, 1 <= B <= 2^20, 1 <= K <= 8.  Before anything is enqueued: a null
+ * pointer (other than g2 with G2 = 0; g2 given with G2 = 0 as well), a pointer not aligned to its type (workspace: 16
+ * bytes), N < 2, B < 1, G1 < 1, G2 < 0, K < 1, a beta that is not positive and finite -> NPLDA_EINVAL; a size past the
+ * limits -> NPLDA_EUNSUPPORTED; workspace_bytes < nplda_bootstrap_workspace_bytes(N, G1, G2, B) -> NPLDA_ENOSPC.
+ * nplda_bootstrap_workspace_bytes needs no device, returns 0 outside the limits, does not decrease with N and does not
+ * depend on B inside them (the replicates are processed in tiles that reuse one table and one set of partials). */
+size_t nplda_bootstrap_workspace_bytes(int64_t N, int64_t G1, int64_t G2, int B);
+int nplda_bootstrap_run(void);  /* sorted positions one wave walks (per-run partials): tests straddle its multiples */
+int nplda_bootstrap_tile(void); /* replicates per tile, row 0 included: tests straddle its multiples */
+int nplda_bootstrap_f32(const float* scores, const float* target, const int32_t* g1, const int32_t* g2, int64_t N, int64_t G1,
+                        int64_t G2, int B, uint64_t seed, const double* betas, int K, int is_llr, double* out,
+                        int64_t* totals, void* workspace, size_t workspace_bytes, nplda_stream_t stream);
+
 /* ---- host-side text I/O of the trial-list path (no device work; plain host pointers) ------------------------------ */
 
 /* Rows and columns of a whitespace-separated table held in memory, with np.genfromtxt(dtype=str) semantics (the

@@ -99,6 +99,11 @@ SIGNATURES = {
                                           _c_sz, _c_int, _c_vp]),
     **{f"nplda_pav_apply_{p}": (_c_int, [_c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_int, _c_vp])
        for p in ("f32", "f64")},
+    "nplda_bootstrap_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_int]),
+    "nplda_bootstrap_run": (_c_int, []),
+    "nplda_bootstrap_tile": (_c_int, []),
+    "nplda_bootstrap_f32": (_c_int, [_c_f32p, _c_f32p, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, ctypes.c_uint64,
+                                     ctypes.POINTER(ctypes.c_double), _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),
     "nplda_text_scan": (_c_i64, [ctypes.c_char_p, _c_sz, ctypes.POINTER(_c_int)]),
     "nplda_text_lookup": (_c_int, [ctypes.c_char_p, _c_sz, _c_i64, _c_int, _c_int, _c_int, ctypes.c_char_p, _c_vp, _c_vp,
                                    _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64)]),

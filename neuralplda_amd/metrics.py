@@ -22,6 +22,12 @@ design/k18_pav_rocch.md), for arbitrary scores:
 
 * min_cllr(scores, target): the Cllr of the best monotone map of the scores (PAV); cllr - min_cllr is the calibration loss.
 * rocch_eer(scores, target): the equal error rate on the ROC convex hull; rocch(scores, target): the hull's vertices.
+
+Confidence intervals (kernels nplda_bootstrap_*, csrc/nplda_bootstrap.hip, design/k20_bootstrap.md):
+
+* bootstrap(scores, target, groups1, groups2): EER, min cost (and with llr=True actual cost and Cllr) of n_boot
+  resamplings of the groups of both trial sides; bootstrap_ci: percentile intervals; bootstrap_diff: the paired
+  comparison of two systems on the same trials under the same resamplings.
 """
 import math
 
@@ -29,7 +35,8 @@ import torch
 
 from . import _lib, ops
 
-__all__ = ["minc", "eer", "minc_exact", "cllr", "act_cost", "act_dcf", "min_cllr", "rocch_eer", "rocch"]
+__all__ = ["minc", "eer", "minc_exact", "cllr", "act_cost", "act_dcf", "min_cllr", "rocch_eer", "rocch", "bootstrap",
+           "bootstrap_ci", "bootstrap_diff", "BootstrapResult"]
 
 
 def _on_device(output, target):
@@ -178,3 +185,127 @@ def rocch(scores, target):
     T = np.concatenate(([0], np.cumsum(t))).astype(np.float64)
     F = np.concatenate(([0], np.cumsum(n - t))).astype(np.float64)
     return 1.0 - F / rep["n_non"], T / rep["n_tgt"]
+
+
+class BootstrapResult:
+    """Replicates of one bootstrap call.  columns: {name: (n_boot + 1,) float64 array}, row 0 the point estimate, the
+    row of a degenerate replicate (a class left empty by the draw) NaN; names are "min_cost_<beta>" and "eer", then with
+    llr "act_cost_<beta>" and "cllr".  totals: (n_boot + 1, 2) int64, the weighted numbers of targets and non-targets."""
+
+    def __init__(self, columns, totals, betas=(), seed=0):
+        import numpy as np
+        self.columns = {k: np.asarray(v, dtype=np.float64) for k, v in columns.items()}
+        self.totals = np.asarray(totals, dtype=np.int64)
+        self.betas = tuple(betas)
+        self.seed = seed
+        n = {v.shape for v in self.columns.values()}
+        if len(n) != 1 or len(next(iter(n))) != 1 or self.totals.shape != (next(iter(n))[0], 2):
+            raise ValueError("columns must be equally long vectors with one row of totals each")
+
+    @property
+    def n_boot(self):
+        return self.totals.shape[0] - 1
+
+    @property
+    def degenerate(self):
+        """Which replicates (of rows 1 .. n_boot) are degenerate: a boolean array."""
+        import numpy as np
+        bad = np.zeros(self.n_boot, dtype=bool)
+        for v in self.columns.values():
+            bad |= np.isnan(v[1:])
+        return bad
+
+    @property
+    def n_degenerate(self):
+        return int(self.degenerate.sum())
+
+    def __getitem__(self, name):
+        return self.columns[name]
+
+
+def _group_ids(groups, N, dev, name):
+    """-> (int32 device tensor of ids in [0, G), G).  Integer tensors / arrays are ids as given (G = max + 1); anything
+    else (strings) is mapped with np.unique; None is one group per trial."""
+    import numpy as np
+    if groups is None:
+        return torch.arange(N, dtype=torch.int32, device=dev), N
+    if isinstance(groups, torch.Tensor):
+        if groups.dtype.is_floating_point or groups.dtype == torch.bool:
+            raise TypeError(f"{name} must hold integer ids or strings")
+        g = groups.detach().reshape(-1)
+        if g.numel() != N:
+            raise ValueError(f"{name} must hold one id per trial")
+        if N and int(g.min()) < 0:
+            raise ValueError(f"{name} holds a negative id")
+        return g.to(dev, torch.int32), (int(g.max()) + 1 if N else 0)
+    a = np.asarray(groups).reshape(-1)
+    if a.size != N:
+        raise ValueError(f"{name} must hold one id per trial")
+    if a.dtype.kind in "iu":
+        if N and int(a.min()) < 0:
+            raise ValueError(f"{name} holds a negative id")
+        return torch.from_numpy(a.astype(np.int32)).to(dev), (int(a.max()) + 1 if N else 0)
+    u, inv = np.unique(a, return_inverse=True)
+    return torch.from_numpy(inv.reshape(-1).astype(np.int32)).to(dev), int(u.size)
+
+
+def _column_names(betas, llr):
+    names = [f"min_cost_{b:g}" for b in betas] + ["eer"]
+    if llr:
+        names += [f"act_cost_{b:g}" for b in betas] + ["cllr"]
+    return names
+
+
+def bootstrap(scores, target, groups1, groups2=None, n_boot=1000, seed=0, betas=(99.0, 199.0), llr=False):
+    """Group bootstrap of the detection metrics -> BootstrapResult.  groups1 / groups2: the group (speaker) of each
+    trial's two sides, as integer ids or as arrays of names; every replicate redraws the groups of each side with
+    replacement and weighs a trial by the product of the draw counts of its two groups.  groups2=None resamples side 1
+    alone, groups1=None resamples trials (one group per trial, within the kernel's group limit)."""
+    betas = [float(b) for b in betas]
+    if len(set(_column_names(betas, llr))) != len(_column_names(betas, llr)):
+        raise ValueError("betas must be distinct")
+    s, t = _on_device(torch.as_tensor(scores), torch.as_tensor(target))
+    N = s.numel()
+    g1, G1 = _group_ids(groups1, N, s.device, "groups1")
+    g2, G2 = (None, 0) if groups2 is None else _group_ids(groups2, N, s.device, "groups2")
+    out, totals, flags = ops.bootstrap_metrics(s, t, g1, G1, g2, G2, n_boot=n_boot, seed=seed, betas=betas, llr=llr)
+    bad, sat = flags.tolist()
+    if bad:
+        raise ValueError(f"{bad} trials have a group id outside the declared range")
+    if sat:
+        raise _lib.NpldaHipError(f"{sat} draw counts exceeded 255: the replicates are not usable")
+    out = out.cpu().numpy()
+    return BootstrapResult({n: out[:, j].copy() for j, n in enumerate(_column_names(betas, llr))}, totals.cpu().numpy(),
+                           betas=betas, seed=seed)
+
+
+def _interval(values, alpha):
+    import numpy as np
+    lo, hi = np.quantile(values, [alpha / 2, 1 - alpha / 2], method="linear")
+    return float(lo), float(hi)
+
+
+def bootstrap_ci(result, alpha=0.05, max_degenerate=0.05, **kwargs):
+    """Percentile intervals -> {name: (point, lo, hi)} over the non-degenerate replicates of a BootstrapResult (or of
+    bootstrap(*result, **kwargs) when `result` is a tuple of its arguments).  Raises when more than the share
+    max_degenerate of the replicates is degenerate: an interval over the rest would be biased."""
+    if not isinstance(result, BootstrapResult):
+        result = bootstrap(*result, **kwargs)
+    if not 0.0 < alpha < 1.0:
+        raise ValueError("alpha must lie strictly between 0 and 1")
+    bad = result.degenerate
+    if result.n_boot < 1 or bad.sum() > max_degenerate * result.n_boot or bad.all():
+        raise ValueError(f"{int(bad.sum())} of {result.n_boot} replicates are degenerate (a class left empty); "
+                         f"the allowed share is {max_degenerate}")
+    return {n: (float(v[0]),) + _interval(v[1:][~bad], alpha) for n, v in result.columns.items()}
+
+
+def bootstrap_diff(scores_a, scores_b, target, groups1, groups2=None, n_boot=1000, seed=0, betas=(99.0, 199.0), llr=False,
+                   alpha=0.05, max_degenerate=0.05):
+    """Paired comparison of two systems on the same trials: two bootstrap calls with one seed, hence the same weights ->
+    (diff: BootstrapResult of a - b per replicate, {name: (point, lo, hi, excludes_zero)})."""
+    ra = bootstrap(scores_a, target, groups1, groups2, n_boot=n_boot, seed=seed, betas=betas, llr=llr)
+    rb = bootstrap(scores_b, target, groups1, groups2, n_boot=n_boot, seed=seed, betas=betas, llr=llr)
+    diff = BootstrapResult({n: ra.columns[n] - rb.columns[n] for n in ra.columns}, ra.totals, betas=ra.betas, seed=seed)
+    ci = bootstrap_ci(diff, alpha=alpha, max_degenerate=max_degenerate)
+    return diff, {n: (p, lo, hi, bool(lo > 0.0 or hi < 0.0)) for n, (p, lo, hi) in ci.items()}

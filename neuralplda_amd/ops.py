@@ -1892,3 +1892,69 @@ def pav_apply(scores, lo, hi, llr, out_dtype=torch.float64):
                                                       _lib.ptr(out), int(out_dtype == torch.float64), _lib.current_stream())
     _lib.check(code, "nplda_pav_apply_" + sfx)
     return out
+
+
+BOOTSTRAP_MAX_K = 8
+
+
+def bootstrap_run():
+    """Sorted positions one wave walks (nplda_bootstrap_run)."""
+    return int(_lib.load().nplda_bootstrap_run())
+
+
+def bootstrap_tile():
+    """Replicates per tile, the point estimate included (nplda_bootstrap_tile)."""
+    return int(_lib.load().nplda_bootstrap_tile())
+
+
+def _group_ids(g, name, N, dev):
+    if not isinstance(g, torch.Tensor) or not g.is_cuda or g.dtype != torch.int32:
+        raise TypeError(f"{name} must be an int32 tensor on a HIP device")
+    g = g.detach().reshape(-1).contiguous()
+    if g.numel() != N or g.device != dev:
+        raise ValueError(f"{name} must hold one group id per trial, on the device of the scores")
+    return g
+
+
+def bootstrap_metrics(scores, target, g1, G1, g2=None, G2=0, n_boot=1000, seed=0, betas=(1.0,), llr=False):
+    """nplda_bootstrap_f32: scores, target (N,) fp32, g1 / g2 (N,) int32 group ids in [0, G1) / [0, G2) (g2 None: one
+    side) -> (out (n_boot + 1, ncol) fp64, totals (n_boot + 1, 2) int64, flags (2,) int64), device tensors; nothing is
+    read back.  Columns: min cost per beta, EER, then with llr the actual cost per beta and Cllr; row 0 is the point
+    estimate.  flags: trials with a group id out of range (excluded), draw counts that saturated."""
+    lib = _lib.load()
+    _require_dev_f32(scores, "scores")
+    s = scores.detach().reshape(-1).contiguous()
+    N = s.numel()
+    t = _calib_target(target, N, s.device)
+    g1 = _group_ids(g1, "g1", N, s.device)
+    G1, G2 = int(G1), int(G2)
+    if g2 is None:
+        if G2 != 0:
+            raise ValueError("G2 must be 0 without g2")
+    else:
+        g2 = _group_ids(g2, "g2", N, s.device)
+        if G2 < 1:
+            raise ValueError("g2 needs its number of groups G2 >= 1")
+    betas = [float(b) for b in betas]
+    K, B = len(betas), int(n_boot)
+    if K < 1:
+        raise ValueError("at least one beta")
+    if K > BOOTSTRAP_MAX_K:
+        raise _lib.NpldaHipError(f"{K} cost ratios are outside the compiled kernel set (1 .. {BOOTSTRAP_MAX_K})")
+    if B < 1:
+        raise ValueError("n_boot must be at least 1")
+    nbytes = lib.nplda_bootstrap_workspace_bytes(N, G1, G2, B)
+    if nbytes == 0:
+        raise _lib.NpldaHipError(f"N = {N}, G1 = {G1}, G2 = {G2}, n_boot = {B} are outside the supported range "
+                                 "(2 <= N < 2^31, 1 <= G <= 2^20, n_boot <= 2^20)")
+    ncol = K + 1 + (K + 1 if llr else 0)
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=s.device)
+    out = torch.empty((B + 1, ncol), dtype=torch.float64, device=s.device)
+    totals = torch.empty((B + 1, 2), dtype=torch.int64, device=s.device)
+    barr = (ctypes.c_double * K)(*betas)
+    with _lib.on_device(s.device):
+        code = lib.nplda_bootstrap_f32(_lib.ptr(s), _lib.ptr(t), _lib.ptr(g1), _lib.ptr(g2), N, G1, G2, B,
+                                       int(seed) & 0xffffffffffffffff, barr, K, 1 if llr else 0, _lib.ptr(out),
+                                       _lib.ptr(totals), _lib.ptr(ws), nbytes, _lib.current_stream())
+    _lib.check(code, "nplda_bootstrap_f32")
+    return out, totals, ws[:2]
