@@ -1145,6 +1145,44 @@ def cohort_stats(z_rows, q_rows, z_coh, q_coh, packed, topn=500, select="lowest"
     return stats
 
 
+def cohort_scores(z_rows, q_rows, z_coh, q_coh, packed):
+    """The (R, M) float32 cohort score matrix S = q_r + q_m + 2 (z_r * P) z_m^T as the spilling path of
+    nplda_cohort_stats_f32 writes it (diagnostics and tests; the reference reads this table from a file).  The call asks
+    for top-N = M, which no shape's fused plan accepts, and brings a workspace of exactly the control block + R score rows:
+    one chunk, whose rows are returned as a view of the workspace (row stride M rounded up to 4).  A matrix above 4 GiB is
+    walked in row chunks and copied out."""
+    lib = _lib.load()
+    _need_fp32(packed, "cohort_scores")
+    for n, t in (("z_rows", z_rows), ("q_rows", q_rows), ("z_coh", z_coh), ("q_coh", q_coh)):
+        _require_dev_f32(t, n)
+    if z_rows.stride(0) != packed.ldz or z_coh.stride(0) != packed.ldz:
+        raise ValueError("z tables must come from embed() (row stride = packed.ldz)")
+    R, M = z_rows.shape[0], z_coh.shape[0]
+    dev = z_rows.device
+    if R == 0 or M == 0:
+        return torch.empty((R, M), dtype=torch.float32, device=dev)
+    lds = (M + 3) // 4 * 4
+    ctl = 64  # floats of the control block in front of the score rows (kCohortCtlBytes, csrc/nplda_cohort.hip)
+    rows_per = max(1, min(R, (4 << 30) // (lds * 4)))
+    q_rows, q_coh = q_rows.contiguous(), q_coh.contiguous()
+    stats = torch.empty((rows_per, 4), dtype=torch.float64, device=dev)
+    out = None if rows_per == R else torch.empty((R, M), dtype=torch.float32, device=dev)
+    for r0 in range(0, R, rows_per):
+        rc = min(rows_per, R - r0)
+        ws = torch.empty(ctl + rc * lds, dtype=torch.float32, device=dev)
+        with _lib.on_device(dev):
+            code = lib.nplda_cohort_stats_f32(_lib.ptr(z_rows[r0:r0 + rc]), _lib.ptr(q_rows[r0:r0 + rc]), rc, _lib.ptr(z_coh),
+                                              _lib.ptr(q_coh), M, packed.ldz, _lib.ptr(packed.buf), packed.D0, packed.D1,
+                                              packed.D2, M, 1, _lib.ptr(stats), _lib.ptr(ws), ws.numel() * 4,
+                                              _lib.current_stream())
+        _lib.check(code, "nplda_cohort_stats_f32")
+        S = ws[ctl:].view(rc, lds)[:, :M]
+        if out is None:
+            return S
+        out[r0:r0 + rc] = S
+    return out
+
+
 TOPK_MAX_K = 128  # NPLDA_TOPK_MAX_K, include/nplda_hip.h
 _TOPK_MASKS = {None: 0, "different": 1, "same": 2}
 
