@@ -1000,6 +1000,49 @@ int nplda_class_scatter_f32(const float* table, int64_t table_rows, int64_t ldt,
                             const int64_t* offs, int64_t S, int n, const float* pivot, double* sum, double* scatter,
                             double* class_sum, int accumulate, void* ws, size_t ws_bytes, nplda_stream_t stream);
 
+/* ---- dense score matrix of a set against itself, and its agglomerative clustering ---------------------------- */
+
+/* csrc/nplda_ahc.hip, design/k21_ahc.md.  One call handles P independent PROBLEMS: problem p owns the contiguous rows
+ * offsets[p] .. offsets[p + 1] of an embedding table (z, q from nplda_embed_f32, row stride ldz); n_p = 0 and 1 are legal;
+ * row indices in every output are local to the problem.  `offsets_host` (P + 1 int64, offsets_host[0] == 0, non-decreasing)
+ * is read by the host during the call only: it sizes the launch and is what the argument checks see; `offsets` is the same
+ * array in DEVICE memory.  The matrices of the problems lie one after the other, problem p's n_p x n_p floats (row stride
+ * n_p) at element sum_{r < p} n_r^2.  Caller-owned workspace, nothing allocated, no host synchronisation, capturable, the same
+ * bits on every call, no floating-point atomics; every output word is written by the call (no memset), nothing is read back.
+ * P == 0 or an empty table is a no-op; every error is a status code before any launch. */
+typedef struct nplda_ahc_merge {
+    int32_t a, b;       /* the clusters merged, named by their smallest member rows, a < b; b is absorbed into a */
+    double value;       /* the linkage value of the pair */
+    int32_t size_after; /* members of a after the merge */
+    int32_t reserved;   /* written as 0 */
+} nplda_ahc_merge;
+#define NPLDA_AHC_AVERAGE  0  /* S(A, B) / (|A| |B|): fp64 sums of member-pair scores, ONE addition per surviving cluster and merge */
+#define NPLDA_AHC_COMPLETE 1  /* the minimum member-pair score */
+#define NPLDA_AHC_SINGLE   2  /* the maximum member-pair score */
+int nplda_ahc_max_n(void);  /* the largest n_p (16384: the fp64 numerators of a problem take 8 n_p^2 bytes) */
+int nplda_ahc_block(void);  /* threads of the clustering workgroup (one workgroup per problem) */
+int nplda_ahc_small_n(void); /* problems above this many rows scan a row again with the whole workgroup, the others with one wave */
+/* Bytes of the matrices / workspace bytes of the clustering for these problems; 0 where the offsets are not acceptable
+ * (the workspace of acceptable offsets is never 0). */
+size_t nplda_score_matrix_bytes(const int64_t* offsets_host, int64_t P);
+size_t nplda_ahc_workspace_bytes(const int64_t* offsets_host, int64_t P);
+/* out = the score matrices s_ij = q_i + q_j + 2 sum_d P_d z_id z_jd of the problems.  Only 16 x 16 pieces that hold some
+ * i < j are formed, with the lower index as the row operand and the products and feature order of nplda_topk_scores_f32,
+ * so that for i < j the bits are what that call returns for (row i, column j); entry (j, i) is a copy of (i, j) and the
+ * diagonal is +0.0f.  Rows of another problem are never read; pad columns D2 .. ldz meet P = 0. */
+int nplda_score_matrix_f32(const float* z, int64_t ldz, const float* q, const int64_t* offsets_host, const int64_t* offsets,
+                           int64_t P, const void* packed, int D0, int D1, int D2, float* out, nplda_stream_t stream);
+/* Agglomerative clustering of every problem under its matrix in S (the layout above; only the strict upper triangle is
+ * read; NaN scores are outside the contract).  Each step merges the pair of live clusters (a, b), a < b, with the LARGEST
+ * linkage value, the lexicographically lowest (a, b) among equal values, and stops before the first merge whose value is
+ * < threshold or when min_clusters clusters remain.  merges: sum of max(n_p - 1, 0) records, problem by problem, the ones not
+ * executed (-1, -1, NaN, 0); n_merges, n_clusters: P int32; labels: one int32 per table row, the dense rank of the row's
+ * cluster in order of the clusters' smallest members.  A NaN threshold, min_clusters < 1 or an unknown linkage is
+ * NPLDA_EINVAL, n_p above nplda_ahc_max_n() NPLDA_EUNSUPPORTED, a short workspace NPLDA_ENOSPC.  ws: 16-byte aligned. */
+int nplda_ahc_f32(const float* S, const int64_t* offsets_host, const int64_t* offsets, int64_t P, int linkage, double threshold,
+                  int min_clusters, nplda_ahc_merge* merges, int32_t* n_merges, int32_t* n_clusters, int32_t* labels, void* ws,
+                  size_t ws_bytes, nplda_stream_t stream);
+
 /* ---- measurement utility ------------------------------------------------------------------------------------- */
 
 /* Shader-clock probe for bench.py (no reference counterpart): one wave that stays resident for window_us microseconds

@@ -187,6 +187,15 @@ SIGNATURES = {
     "nplda_topk_scores_f32": (_c_int, [_c_f32p, _c_f32p, _c_i64, _c_f32p, _c_f32p, _c_i64, _c_i64, _c_vp, _c_int, _c_int,
                                        _c_int, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_f32p, _c_vp,
                                        _c_vp, _c_sz, _c_vp]),
+    "nplda_ahc_max_n": (_c_int, []),
+    "nplda_ahc_block": (_c_int, []),
+    "nplda_ahc_small_n": (_c_int, []),
+    "nplda_score_matrix_bytes": (_c_sz, [_c_vp, _c_i64]),
+    "nplda_ahc_workspace_bytes": (_c_sz, [_c_vp, _c_i64]),
+    "nplda_score_matrix_f32": (_c_int, [_c_f32p, _c_i64, _c_f32p, _c_vp, _c_vp, _c_i64, _c_vp, _c_int, _c_int, _c_int, _c_f32p,
+                                        _c_vp]),
+    "nplda_ahc_f32": (_c_int, [_c_f32p, _c_vp, _c_vp, _c_i64, _c_int, ctypes.c_double, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
+                               _c_sz, _c_vp]),
     "nplda_matrix_frag_bytes": (_c_sz, [_c_int, _c_int]),
     "nplda_pack_matrix_f32": (_c_int, [_c_f32p, _c_i64, _c_int, _c_int, _c_int, _c_vp, _c_sz, _c_vp]),
     "nplda_dplda_quadform_f32": (_c_int, [_c_f32p, _c_int, _c_vp, _c_sz, _c_f32p, _c_vp]),

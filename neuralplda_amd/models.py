@@ -565,6 +565,12 @@ class NeuralPlda(nn.Module):
             raise ValueError("the Gallery was built with another model")
         return g.search(x_probe, k=k)
 
+    def cluster(self, x, groups=None, threshold=float("-inf"), min_clusters=1, linkage="average"):
+        """Agglomerative clustering of the rows of x under this model's score, each group on its own -> cluster.Clustering
+        (labels, the merge records, .cut, .spk2utt): pseudo-speakers for every spk2utt consumer."""
+        from . import cluster
+        return cluster.cluster(self, x, groups=groups, threshold=threshold, min_clusters=min_clusters, linkage=linkage)
+
     def cdet(self, output, target):
         """utils/models.py:401-404: hard detection cost at the model thresholds (strict < / >)."""
         dev = _compute_device(output, target)
@@ -692,6 +698,9 @@ class DPlda(NeuralPlda):
     def identify(self, x_probe, gallery_or_xvectors, k=10):
         raise NotImplementedError("identify searches with the NeuralPlda score (P_sqrt, Q); DPlda has a quadratic-form head")
 
+    def cluster(self, x, **kw):
+        raise NotImplementedError("cluster scores with the NeuralPlda score (P_sqrt, Q); DPlda has a quadratic-form head")
+
     def LoadParamsFromKaldi(self, mean_vec_file, transform_mat_file):
         """utils/models.py:551-564."""
         kaldi_format.fold_init(self, mean_vec_file, transform_mat_file)
@@ -769,6 +778,10 @@ class GaussianBackend(nn.Module):
     def identify(self, x_probe, gallery_or_xvectors, k=10):
         raise NotImplementedError("identify searches with the NeuralPlda score (P_sqrt, Q); the Gaussian back end scores a "
                                   "pair from its paired statistics")
+
+    def cluster(self, x, **kw):
+        raise NotImplementedError("cluster scores with the NeuralPlda score (P_sqrt, Q); the Gaussian back end scores a pair "
+                                  "from its paired statistics")
 
     def forward_getpaired(self, x1, x2):
         """utils/models.py:595-601: [normalize(LDA x1), normalize(LDA x2)] -> (B, 2 D1)."""

@@ -1242,6 +1242,115 @@ def topk_scores(z_rows, q_rows, z_tab, q_tab, packed, k, largest=True, labels=No
     return vals, idx
 
 
+AHC_LINKAGES = {"average": 0, "complete": 1, "single": 2}  # NPLDA_AHC_*, include/nplda_hip.h
+# nplda_ahc_merge as a numpy record (24 bytes)
+AHC_MERGE_DTYPE = [("a", "<i4"), ("b", "<i4"), ("value", "<f8"), ("size_after", "<i4"), ("reserved", "<i4")]
+
+
+class RaggedOffsets:
+    """The row offsets of P independent problems over one table, on the host (int64 numpy, what the C entry points check and
+    size their launches by) and on a device (what the kernels read).  Make one outside a graph capture: building it copies
+    from the host."""
+
+    __slots__ = ("host", "dev", "P", "rows", "elems", "records")
+
+    def __init__(self, offsets, device):
+        import numpy as np
+        host = np.ascontiguousarray(np.asarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets, dtype=np.int64))
+        if host.ndim != 1 or host.size < 1 or host[0] != 0 or (np.diff(host) < 0).any():
+            raise ValueError("offsets must be P + 1 non-decreasing row offsets that start at 0")
+        lib = _lib.load()
+        self.host, self.P, self.rows = host, host.size - 1, int(host[-1])
+        if self.P and int(np.diff(host).max()) > lib.nplda_ahc_max_n():
+            raise ValueError(f"a problem may have at most {lib.nplda_ahc_max_n()} rows")
+        n = np.diff(host)
+        self.elems, self.records = int((n * n).sum()), int(np.maximum(n - 1, 0).sum())
+        self.dev = torch.from_numpy(host).to(device)
+
+    @property
+    def hptr(self):
+        return self.host.ctypes.data
+
+
+def _ragged(offsets, rows, dev):
+    if offsets is None:
+        offsets = [0, rows]
+    if not isinstance(offsets, RaggedOffsets):
+        offsets = RaggedOffsets(offsets, dev)
+    if offsets.dev.device != dev:
+        raise ValueError("the offsets live on another device")
+    return offsets
+
+
+def score_matrix(z, q, packed, offsets=None):
+    """nplda_score_matrix_f32: the dense score matrix of every problem's rows against themselves, exactly symmetric with a
+    +0.0 diagonal; for i < j the bits of topk_scores (row i, column j).  z, q come from embed(); offsets: P + 1 row offsets
+    (a sequence or a RaggedOffsets) -> the matrices one after the other in a flat float32 tensor (problem p's n_p x n_p at
+    element sum n_r^2 of the problems before it); None: the whole table is one problem -> (N, N)."""
+    lib = _lib.load()
+    _need_fp32(packed, "score_matrix")
+    _require_dev_f32(z, "z")
+    _require_dev_f32(q, "q")
+    if z.dim() != 2 or z.shape[1] != packed.ldz or (z.shape[0] > 1 and z.stride(0) != packed.ldz) or z.stride(1) != 1:
+        raise ValueError(f"z must come from embed() (shape (rows, {packed.ldz}), row stride = packed.ldz)")
+    N, dev = z.shape[0], z.device
+    if q.shape != (N,) or packed.device != dev:
+        raise ValueError("q must hold one self term per row of z, on the device of z and the packed model")
+    single = offsets is None
+    offs = _ragged(offsets, N, dev)
+    if offs.rows != N:
+        raise ValueError(f"the offsets cover {offs.rows} rows, z has {N}")
+    out = torch.empty(offs.elems, dtype=torch.float32, device=dev)
+    if offs.elems:
+        with _lib.on_device(dev):
+            code = lib.nplda_score_matrix_f32(_lib.ptr(z), packed.ldz, _lib.ptr(q.contiguous()), offs.hptr, _lib.ptr(offs.dev),
+                                              offs.P, _lib.ptr(packed.buf), packed.D0, packed.D1, packed.D2, _lib.ptr(out),
+                                              _lib.current_stream())
+        _lib.check(code, "nplda_score_matrix_f32")
+    return out.view(N, N) if single else out
+
+
+def ahc(S, offsets=None, linkage="average", threshold=float("-inf"), min_clusters=1):
+    """nplda_ahc_f32: agglomerative clustering of every problem under its float32 score matrix in S (the layout of
+    score_matrix; only the strict upper triangle is read) -> (merges, n_merges (P,), n_clusters (P,), labels (rows,)), all on
+    the device.  merges is a uint8 tensor (records, 24): view its host copy with AHC_MERGE_DTYPE.  Each step merges the pair
+    with the LARGEST linkage value (lowest (a, b) among equal ones); it stops before the first value < threshold or at
+    min_clusters clusters."""
+    lib = _lib.load()
+    _require_dev_f32(S, "S")
+    if linkage not in AHC_LINKAGES:
+        raise ValueError(f"linkage must be one of {sorted(AHC_LINKAGES)}")
+    threshold, min_clusters = float(threshold), int(min_clusters)
+    if threshold != threshold or min_clusters < 1:
+        raise ValueError("threshold must not be NaN and min_clusters must be at least 1")
+    if not S.is_contiguous():
+        S = S.contiguous()
+    dev = S.device
+    if offsets is None:
+        if S.dim() != 2 or S.shape[0] != S.shape[1]:
+            raise ValueError("without offsets S must be one square matrix")
+        offsets = [0, S.shape[0]]
+    offs = _ragged(offsets, 0, dev)
+    if S.numel() != offs.elems:
+        raise ValueError(f"S holds {S.numel()} scores, the offsets ask for {offs.elems}")
+    merges = torch.empty((offs.records, 24), dtype=torch.uint8, device=dev)
+    n_merges = torch.empty(offs.P, dtype=torch.int32, device=dev)
+    n_clusters = torch.empty(offs.P, dtype=torch.int32, device=dev)
+    labels = torch.empty(offs.rows, dtype=torch.int32, device=dev)
+    if offs.P == 0:
+        return merges, n_merges, n_clusters, labels
+    wsb = lib.nplda_ahc_workspace_bytes(offs.hptr, offs.P)
+    if wsb == 0:
+        raise _lib.NpldaHipError("ahc: the offsets are outside what the kernel takes")
+    ws = torch.empty(wsb // 8 if offs.records else 2, dtype=torch.float64, device=dev)
+    with _lib.on_device(dev):
+        code = lib.nplda_ahc_f32(_lib.ptr(S), offs.hptr, _lib.ptr(offs.dev), offs.P, AHC_LINKAGES[linkage], threshold,
+                                 min_clusters, _lib.ptr(merges), _lib.ptr(n_merges), _lib.ptr(n_clusters), _lib.ptr(labels),
+                                 _lib.ptr(ws), ws.numel() * 8, _lib.current_stream())
+    _lib.check(code, "nplda_ahc_f32")
+    return merges, n_merges, n_clusters, labels
+
+
 def row_stats(S, topn=500, select="lowest"):
     """nplda_row_stats_f32 on an explicit (R, M) float32 score matrix."""
     lib = _lib.load()
