@@ -1043,6 +1043,47 @@ int nplda_ahc_f32(const float* S, const int64_t* offsets_host, const int64_t* of
                   int min_clusters, nplda_ahc_merge* merges, int32_t* n_merges, int32_t* n_clusters, int32_t* labels, void* ws,
                   size_t ws_bytes, nplda_stream_t stream);
 
+/* ---- VB-HMM resegmentation of clustered embeddings (VBx) ----------------------------------------------------- */
+
+/* csrc/nplda_vbhmm.hip, design/k22_vbhmm.md.  One call handles P independent PROBLEMS (recordings) with the conventions of
+ * nplda_ahc_f32: problem p owns the rows offsets[p] .. offsets[p + 1] of z IN TIME ORDER (T_p of them) and the speaker slots
+ * spk_offsets[p] .. spk_offsets[p + 1] (S_p of them); both offset arrays are given on the host (read during the call only:
+ * checks and sizes) and on the device.  z is what nplda_embed_f32 wrote (fp32, 16-byte aligned, row stride ldz >= D2, a
+ * multiple of 4): rows in the space where the within-class covariance is I and the between-class covariance diag(psi);
+ * columns D2 .. ldz and rows of another problem are never read.  psi: D2 float64 on the device, >= 0.
+ *
+ * Per problem, in float64 throughout, iteration i = 0, 1, ...: speaker models from the posteriors (N_s, invL_sd, alpha_sd),
+ * emissions l_ts, a forward-backward pass over the HMM with transition loop_prob [i = j] + (1 - loop_prob) pi_j (normalised
+ * at every step; speakers with pi_s == 0 stay exactly dead), ELBO_i, the update of pi; for i >= 1 it stops after the
+ * iteration whose ELBO gain is < epsilon (-inf: never), else after max_iters.  Initial posteriors: gamma_init (the layout of
+ * gamma), or from labels_init (one int32 per table row, local to the problem): softmax_s(init_smoothing [s = label]), a
+ * label outside 0 .. S_p - 1 gives the uniform row.  EXACTLY ONE of the two is non-null.  pi_init (the layout of pi) may be
+ * null: 1 / S_p.
+ *
+ * Outputs, every word written by the call: gamma (float64, problem p's T_p x S_p block at element sum_{r < p} T_r S_r),
+ * pi (float64, at spk_offsets[p]), elbo (P x max_iters float64, NaN where not executed), n_iters (P int32), labels (one
+ * int32 per table row: argmax_s gamma_ts, the lowest s among equal values, renumbered to the dense rank of the speakers
+ * that own a row, in order of s), n_speakers (P int32).  T_p == 0 writes n_iters = 0, n_speakers = 0 and a NaN elbo row
+ * only.  Rows with NaN are outside the contract.
+ *
+ * NPLDA_EINVAL: NaN epsilon, Fa or Fb not > 0 (or not finite), loop_prob outside [0, 1), init_smoothing < 0 or NaN,
+ * max_iters < 1, bad offsets, S_p == 0 with T_p > 0, a null or misaligned pointer, both or neither initialiser.
+ * NPLDA_EUNSUPPORTED: S_p above nplda_vbhmm_max_speakers(), max_iters above nplda_vbhmm_max_iters(), T_p above
+ * nplda_ahc_max_n(), D2 above nplda_max_dim().  NPLDA_ENOSPC: a short workspace.  ws: 16-byte aligned.  Caller-owned
+ * workspace, nothing allocated, no host synchronisation, capturable, the same bits on every call, no floating-point
+ * atomics, no memset, nothing read back; P == 0 is a no-op; every error is a status code before any launch. */
+int nplda_vbhmm_max_speakers(void); /* 64: a speaker per lane of one wave in the recursions */
+int nplda_vbhmm_max_iters(void);    /* 256 */
+int nplda_vbhmm_block(void);        /* threads of the workgroup (one workgroup per problem) */
+/* 0 where the arguments are not acceptable, never 0 for acceptable ones, a multiple of 256 */
+size_t nplda_vbhmm_workspace_bytes(const int64_t* offsets_host, const int64_t* spk_offsets_host, int64_t P, int D2);
+int nplda_vbhmm_f64(const float* z, int64_t ldz, const int64_t* offsets_host, const int64_t* offsets,
+                    const int64_t* spk_offsets_host, const int64_t* spk_offsets, int64_t P, int D2, const double* psi,
+                    const int32_t* labels_init, const double* gamma_init, const double* pi_init, double Fa, double Fb,
+                    double loop_prob, double epsilon, double init_smoothing, int max_iters, double* gamma, double* pi,
+                    double* elbo, int32_t* n_iters, int32_t* labels, int32_t* n_speakers, void* ws, size_t ws_bytes,
+                    nplda_stream_t stream);
+
 /* ---- measurement utility ------------------------------------------------------------------------------------- */
 
 /* Shader-clock probe for bench.py (no reference counterpart): one wave that stays resident for window_us microseconds

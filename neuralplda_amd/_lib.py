@@ -196,6 +196,12 @@ SIGNATURES = {
                                         _c_vp]),
     "nplda_ahc_f32": (_c_int, [_c_f32p, _c_vp, _c_vp, _c_i64, _c_int, ctypes.c_double, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
                                _c_sz, _c_vp]),
+    "nplda_vbhmm_max_speakers": (_c_int, []),
+    "nplda_vbhmm_max_iters": (_c_int, []),
+    "nplda_vbhmm_block": (_c_int, []),
+    "nplda_vbhmm_workspace_bytes": (_c_sz, [_c_vp, _c_vp, _c_i64, _c_int]),
+    "nplda_vbhmm_f64": (_c_int, [_c_f32p, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_vp, _c_vp] +
+                        [ctypes.c_double] * 5 + [_c_int] + [_c_vp] * 7 + [_c_sz, _c_vp]),
     "nplda_matrix_frag_bytes": (_c_sz, [_c_int, _c_int]),
     "nplda_pack_matrix_f32": (_c_int, [_c_f32p, _c_i64, _c_int, _c_int, _c_int, _c_vp, _c_sz, _c_vp]),
     "nplda_dplda_quadform_f32": (_c_int, [_c_f32p, _c_int, _c_vp, _c_sz, _c_f32p, _c_vp]),

@@ -1,4 +1,5 @@
-"""Agglomerative clustering of embeddings under the model's own score (csrc/nplda_ahc.hip, design/k21_ahc.md).
+"""Agglomerative clustering of embeddings under the model's own score (csrc/nplda_ahc.hip, design/k21_ahc.md), and its
+refinement by the Bayesian HMM over each group's rows in time order (VBx: csrc/nplda_vbhmm.hip, design/k22_vbhmm.md).
 
 Unlabelled x-vectors become pseudo-speakers: the set is embedded once (search.embed_table), every group of rows (one
 recording, one domain, or the whole set) is one PROBLEM whose dense score matrix ops.score_matrix writes and ops.ahc
@@ -7,7 +8,7 @@ matrix; the reference has no counterpart."""
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 from .adaptive_score_normalization import _model_params
 from .search import _search_device, embed_table
 
@@ -20,6 +21,18 @@ def _rank_roots(rep):
         root[k] = root[rep[k]]
     rank = np.cumsum(rep == np.arange(n)) - 1
     return rank[root]
+
+
+def _spk2utt(labels, n_clusters, ids, prefix):
+    ids = list(ids)
+    if len(ids) != int(labels.shape[0]):
+        raise ValueError("one id per clustered row")
+    total = int(n_clusters.sum())
+    width = max(4, len(str(max(total - 1, 0))))
+    out = [(f"{prefix}{c:0{width}d}", []) for c in range(total)]
+    for i, c in enumerate(labels.tolist()):
+        out[c][1].append(ids[i])
+    return out
 
 
 class Clustering:
@@ -75,15 +88,7 @@ class Clustering:
     def spk2utt(self, ids, prefix="c"):
         """[(cluster name, [id, ...]), ...] in label order, ids in the caller's row order: what backend.class_layout,
         fit_backend, InitFromXvectors and the loaders take as a spk2utt."""
-        ids = list(ids)
-        if len(ids) != len(self):
-            raise ValueError("one id per clustered row")
-        total = int(self.n_clusters.sum())
-        width = max(4, len(str(max(total - 1, 0))))
-        out = [(f"{prefix}{c:0{width}d}", []) for c in range(total)]
-        for i, c in enumerate(self.labels.tolist()):
-            out[c][1].append(ids[i])
-        return out
+        return _spk2utt(self.labels, self.n_clusters, ids, prefix)
 
 
 def _group_order(groups, N):
@@ -129,3 +134,83 @@ def cluster(model, x, groups=None, threshold=float("-inf"), min_clusters=1, link
     out[order] = local + np.repeat(base, np.diff(offsets))
     rec = merges.cpu().numpy().view(ops.AHC_MERGE_DTYPE).reshape(-1)
     return Clustering(out, n_clusters, rec, offsets, order, n_merges.cpu().numpy())
+
+
+class Refined:
+    """The result of vb_refine(): `labels` (N,) int64 in the CALLER's row order, unique over the whole call (the speakers of
+    group p follow those of group p - 1; inside a group in order of their slot), `n_clusters` (P,) speakers that own a row,
+    `gamma` and `pi` (lists, one per group: (T_p, S_p) posteriors with rows in the group's time order, and (S_p,) priors, over
+    the S_p slots the initial clustering had), `elbo` (P, max_iters; NaN where not executed), `n_iters` (P,), `offsets` and
+    `order` as in Clustering."""
+
+    def __init__(self, labels, n_clusters, gamma, pi, elbo, n_iters, offsets, order):
+        self.labels, self.n_clusters, self.gamma, self.pi, self.elbo = labels, n_clusters, gamma, pi, elbo
+        self.n_iters, self.offsets, self.order = n_iters, offsets, order
+
+    def __len__(self):
+        return int(self.labels.shape[0])
+
+    def spk2utt(self, ids, prefix="c"):
+        """As Clustering.spk2utt."""
+        return _spk2utt(self.labels, self.n_clusters, ids, prefix)
+
+
+def _local_init(init, order, offsets):
+    """(labels (N,) int32 in sorted row order and local to each group, S (P,) slots per group) of a Clustering or of an
+    integer label array (local per group or global: each group's distinct values are ranked)."""
+    N, P = order.size, offsets.size - 1
+    if isinstance(init, Clustering):
+        if len(init) != N or not np.array_equal(init.offsets, offsets) or not np.array_equal(init.order, order):
+            raise ValueError("init must come from cluster() on the same x and groups")
+        S = np.asarray(init.n_clusters, np.int64)
+        base = np.concatenate([[0], np.cumsum(S)])[:-1]
+        return (init.labels[order] - np.repeat(base, np.diff(offsets))).astype(np.int32), S
+    lab = np.asarray(init.cpu() if isinstance(init, torch.Tensor) else init)
+    if lab.shape != (N,) or lab.dtype.kind not in "iu":
+        raise ValueError(f"init must be a Clustering or ({N},) integer labels")
+    lab = lab[order]
+    out, S = np.empty(N, np.int32), np.zeros(P, np.int64)
+    for p in range(P):
+        r0, r1 = int(offsets[p]), int(offsets[p + 1])
+        u, inv = np.unique(lab[r0:r1], return_inverse=True)
+        out[r0:r1], S[p] = inv, u.size
+    return out, S
+
+
+def vb_refine(model, x, init, psi, groups=None, **vb):
+    """Refine a clustering of the rows of x by VB-HMM resegmentation (VBx), each group of `groups` on its own -> Refined.
+    The rows of a group are taken IN THE CALLER'S ORDER, AND THAT ORDER IS THE TIME ORDER of the HMM: pass the segments of a
+    recording in the order they were spoken (groups may interleave; the order inside each group is kept).  `init`: the
+    Clustering that cluster() returned for the same x and groups (over-clustered: its clusters are the speaker slots), or
+    (N,) integer labels, local per group or global.  `psi`: (D2,) between-class variances of the PLDA model in the space of
+    model.extract_plda_embeddings (backend.Backend.psi, kaldi_format.read_plda).  **vb: Fa, Fb, loop_prob, epsilon,
+    init_smoothing, max_iters of ops.vbhmm."""
+    if not hasattr(model, "P_sqrt") or not hasattr(model, "centering_and_wccn_plda"):
+        raise NotImplementedError("vb_refine works on the NeuralPlda embeddings (P_sqrt, Q); this model has another head")
+    dev = _search_device(model, x)
+    with torch.no_grad():
+        packed = ops.pack_params(*_model_params(model, dev))
+    z, _ = embed_table(model, x, packed)
+    N = z.shape[0]
+    order, offsets = _group_order(groups, N)
+    local, S = _local_init(init, order, offsets)
+    limit = int(_lib.load().nplda_vbhmm_max_speakers())
+    if S.size and int(S.max()) > limit:
+        raise ValueError(f"a group has {int(S.max())} clusters, vb_refine takes at most {limit} speaker slots per group: "
+                         f"cut the initial clustering first, e.g. init.cut(n_clusters={limit})")
+    if groups is not None:
+        z = z.index_select(0, torch.from_numpy(order).to(dev))
+    offs = ops.RaggedOffsets(offsets, dev)
+    spk = np.concatenate([[0], np.cumsum(S)]).astype(np.int64)
+    gamma, pi, elbo, n_iters, labels, n_spk = ops.vbhmm(z, offs, ops.RaggedOffsets(spk, dev), psi,
+                                                        labels_init=torch.from_numpy(local).to(dev), **vb)
+    n_spk = n_spk.cpu().numpy()
+    base = np.concatenate([[0], np.cumsum(n_spk)])[:-1]
+    out = np.empty(N, np.int64)
+    out[order] = labels.cpu().numpy().astype(np.int64) + np.repeat(base, np.diff(offsets))
+    T = np.diff(offsets)
+    goff = np.concatenate([[0], np.cumsum(T * S)])
+    gamma, pi = gamma.cpu().numpy(), pi.cpu().numpy()
+    gl = [gamma[goff[p]:goff[p + 1]].reshape(int(T[p]), int(S[p])) for p in range(T.size)]
+    pl = [pi[spk[p]:spk[p + 1]] for p in range(T.size)]
+    return Refined(out, n_spk, gl, pl, elbo.cpu().numpy(), n_iters.cpu().numpy(), offsets, order)

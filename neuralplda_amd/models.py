@@ -571,6 +571,12 @@ class NeuralPlda(nn.Module):
         from . import cluster
         return cluster.cluster(self, x, groups=groups, threshold=threshold, min_clusters=min_clusters, linkage=linkage)
 
+    def vb_refine(self, x, init, psi, **kw):
+        """VB-HMM resegmentation (VBx) of a clustering of the rows of x, each group's rows in time order ->
+        cluster.Refined (cluster.vb_refine)."""
+        from . import cluster
+        return cluster.vb_refine(self, x, init, psi, **kw)
+
     def cdet(self, output, target):
         """utils/models.py:401-404: hard detection cost at the model thresholds (strict < / >)."""
         dev = _compute_device(output, target)
@@ -701,6 +707,9 @@ class DPlda(NeuralPlda):
     def cluster(self, x, **kw):
         raise NotImplementedError("cluster scores with the NeuralPlda score (P_sqrt, Q); DPlda has a quadratic-form head")
 
+    def vb_refine(self, x, init, psi, **kw):
+        raise NotImplementedError("vb_refine works on the NeuralPlda embeddings (P_sqrt, Q); DPlda has a quadratic-form head")
+
     def LoadParamsFromKaldi(self, mean_vec_file, transform_mat_file):
         """utils/models.py:551-564."""
         kaldi_format.fold_init(self, mean_vec_file, transform_mat_file)
@@ -782,6 +791,10 @@ class GaussianBackend(nn.Module):
     def cluster(self, x, **kw):
         raise NotImplementedError("cluster scores with the NeuralPlda score (P_sqrt, Q); the Gaussian back end scores a pair "
                                   "from its paired statistics")
+
+    def vb_refine(self, x, init, psi, **kw):
+        raise NotImplementedError("vb_refine works on the NeuralPlda embeddings (P_sqrt, Q); the Gaussian back end scores a "
+                                  "pair from its paired statistics")
 
     def forward_getpaired(self, x1, x2):
         """utils/models.py:595-601: [normalize(LDA x1), normalize(LDA x2)] -> (B, 2 D1)."""

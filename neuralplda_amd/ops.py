@@ -1351,6 +1351,82 @@ def ahc(S, offsets=None, linkage="average", threshold=float("-inf"), min_cluster
     return merges, n_merges, n_clusters, labels
 
 
+def vbhmm(z, offsets, spk_offsets, psi, labels_init=None, gamma_init=None, pi_init=None, Fa=0.3, Fb=17.0, loop_prob=0.99,
+          epsilon=1e-4, init_smoothing=5.0, max_iters=40):
+    """nplda_vbhmm_f64: VB-HMM resegmentation (VBx) of P problems over one table, all in float64 on the device.  z: (rows, ld)
+    float32 embeddings as embed() wrote them (ld a multiple of 4), problem p's rows offsets[p] .. offsets[p + 1] IN TIME
+    ORDER; spk_offsets: P + 1 offsets of the problems' speaker slots (S_p each, at most nplda_vbhmm_max_speakers());
+    offsets, spk_offsets: sequences or RaggedOffsets (offsets None: the whole table is one problem);
+    psi: (D2,) between-class variances, D2 <= ld.  Exactly one of labels_init ((rows,) integer labels local to the problem;
+    one outside 0 .. S_p - 1 gives the uniform row) and gamma_init (flat float64, the T_p x S_p blocks one after the other).
+    -> (gamma (sum T_p S_p,), pi (sum S_p,), elbo (P, max_iters) with NaN where not executed, n_iters (P,), labels (rows,),
+    n_speakers (P,)), all on the device."""
+    lib = _lib.load()
+    _require_dev_f32(z, "z")
+    if z.dim() != 2 or z.stride(1) != 1 or (z.shape[0] > 1 and z.stride(0) % 4) or z.data_ptr() % 16:
+        raise ValueError("z must be (rows, ld) float32 with unit column stride, a row stride that is a multiple of 4 and a "
+                         "16-byte aligned start: what embed() returns")
+    rows, dev = z.shape[0], z.device
+    ldz = z.stride(0) if rows > 1 else max(z.shape[1] + 3 & ~3, 4)
+    psi = torch.as_tensor(psi)
+    if psi.dim() != 1 or not 1 <= psi.shape[0] <= z.shape[1]:
+        raise ValueError(f"psi must be (D2,) with 1 <= D2 <= {z.shape[1]}, got {tuple(psi.shape)}")
+    D2 = int(psi.shape[0])
+    psi = psi.detach().to(device=dev, dtype=torch.float64).contiguous()
+    Fa, Fb, loop_prob, epsilon, init_smoothing = float(Fa), float(Fb), float(loop_prob), float(epsilon), float(init_smoothing)
+    max_iters = int(max_iters)
+    if not (0.0 < Fa < float("inf") and 0.0 < Fb < float("inf")) or not 0.0 <= loop_prob < 1.0:
+        raise ValueError("Fa and Fb must be positive and finite, loop_prob in [0, 1)")
+    if epsilon != epsilon or not init_smoothing >= 0.0 or not 1 <= max_iters <= lib.nplda_vbhmm_max_iters():
+        raise ValueError(f"epsilon must not be NaN, init_smoothing >= 0, max_iters in 1 .. {lib.nplda_vbhmm_max_iters()}")
+    if (labels_init is None) == (gamma_init is None):
+        raise ValueError("give exactly one of labels_init and gamma_init")
+    offs = _ragged(offsets, rows, dev)
+    if offs.rows != rows:
+        raise ValueError(f"the offsets cover {offs.rows} rows, z has {rows}")
+    spk = _ragged(spk_offsets, 0, dev) if spk_offsets is not None else None
+    if spk is None or spk.P != offs.P:
+        raise ValueError("spk_offsets must give one range of speaker slots per problem")
+    T, S = offs.host[1:] - offs.host[:-1], spk.host[1:] - spk.host[:-1]
+    if ((S == 0) & (T > 0)).any() or (S > lib.nplda_vbhmm_max_speakers()).any():
+        raise ValueError(f"every problem with rows needs 1 .. {lib.nplda_vbhmm_max_speakers()} speaker slots")
+    n_gamma = int((T * S).sum())
+    if labels_init is not None:
+        labels_init = torch.as_tensor(labels_init).to(device=dev, dtype=torch.int32).contiguous()
+        if labels_init.shape != (rows,):
+            raise ValueError("labels_init must hold one label per row of z")
+    else:
+        gamma_init = torch.as_tensor(gamma_init).to(device=dev, dtype=torch.float64).contiguous().view(-1)
+        if gamma_init.numel() != n_gamma:
+            raise ValueError(f"gamma_init holds {gamma_init.numel()} posteriors, the offsets ask for {n_gamma}")
+    if pi_init is not None:
+        pi_init = torch.as_tensor(pi_init).to(device=dev, dtype=torch.float64).contiguous().view(-1)
+        if pi_init.numel() != spk.rows:
+            raise ValueError(f"pi_init holds {pi_init.numel()} priors, the speaker offsets ask for {spk.rows}")
+    gamma = torch.empty(n_gamma, dtype=torch.float64, device=dev)
+    pi = torch.empty(spk.rows, dtype=torch.float64, device=dev)
+    elbo = torch.empty((offs.P, max_iters), dtype=torch.float64, device=dev)
+    n_iters = torch.empty(offs.P, dtype=torch.int32, device=dev)
+    labels = torch.empty(rows, dtype=torch.int32, device=dev)
+    n_speakers = torch.empty(offs.P, dtype=torch.int32, device=dev)
+    if offs.P == 0:
+        return gamma, pi, elbo, n_iters, labels, n_speakers
+    wsb = lib.nplda_vbhmm_workspace_bytes(offs.hptr, spk.hptr, offs.P, D2)
+    if wsb == 0:
+        raise _lib.NpldaHipError("vbhmm: the offsets or D2 are outside what the kernel takes")
+    ws = torch.empty(wsb // 8, dtype=torch.float64, device=dev)
+    if rows == 0:  # no row, no initialiser to read: the entry point still wants exactly one non-null
+        labels_init, gamma_init = torch.zeros(1, dtype=torch.int32, device=dev), None
+    with _lib.on_device(dev):
+        code = lib.nplda_vbhmm_f64(_lib.ptr(z), ldz, offs.hptr, _lib.ptr(offs.dev), spk.hptr, _lib.ptr(spk.dev), offs.P, D2,
+                                   _lib.ptr(psi), _lib.ptr(labels_init), _lib.ptr(gamma_init), _lib.ptr(pi_init), Fa, Fb,
+                                   loop_prob, epsilon, init_smoothing, max_iters, _lib.ptr(gamma), _lib.ptr(pi), _lib.ptr(elbo),
+                                   _lib.ptr(n_iters), _lib.ptr(labels), _lib.ptr(n_speakers), _lib.ptr(ws), wsb,
+                                   _lib.current_stream())
+    _lib.check(code, "nplda_vbhmm_f64")
+    return gamma, pi, elbo, n_iters, labels, n_speakers
+
+
 def row_stats(S, topn=500, select="lowest"):
     """nplda_row_stats_f32 on an explicit (R, M) float32 score matrix."""
     lib = _lib.load()

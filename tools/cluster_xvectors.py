@@ -14,6 +14,12 @@ Merging takes the pair of clusters with the largest linkage value and stops befo
 --min-clusters clusters per recording.  --threshold is in raw score units unless --calibration A B is given: the a and b
 of a score_calibration.fit_linear calibration (llr = a s + b, a > 0).  Average linkage commutes with a positive affine
 map, so a threshold t on calibrated scores is the threshold (t - b) / a on raw ones; nothing else is rescaled.
+--vb-plda FILE: refine the clustering by VB-HMM resegmentation (VBx) under the Kaldi PLDA model in FILE, whose between-class
+variances must belong to the space of the model's embeddings; the utterances of a recording are taken in the order of
+--reco2utt (of the table without it), AND THAT ORDER IS THE TIME ORDER.  Cluster with a high --threshold or a --min-clusters
+above the expected number of speakers (at most 64 clusters per recording): the clusters are the speaker slots the
+refinement starts from.  --vb-fa, --vb-fb, --vb-loop, --vb-max-iters: its scaling factors, self-loop probability and
+iteration limit.
 Output: `utt2spk` (sorted by utterance) and `spk2utt` in --out-dir, what every spk2utt consumer of the package reads."""
 import argparse
 import os
@@ -37,6 +43,11 @@ def main(argv=None):
                     help="--threshold is in units of llr = A s + B (A > 0): it is mapped to (threshold - B) / A")
     ap.add_argument("--min-clusters", type=int, default=1)
     ap.add_argument("--linkage", default="average", choices=["average", "complete", "single"])
+    ap.add_argument("--vb-plda", help="a Kaldi PLDA model: refine the clusters by VB-HMM resegmentation under its psi")
+    ap.add_argument("--vb-fa", type=float, default=0.3)
+    ap.add_argument("--vb-fb", type=float, default=17.0)
+    ap.add_argument("--vb-loop", type=float, default=0.99)
+    ap.add_argument("--vb-max-iters", type=int, default=40)
     ap.add_argument("--prefix", default="c")
     ap.add_argument("--out-dir", required=True)
     ap.add_argument("--device", default="cuda:0")
@@ -65,6 +76,11 @@ def main(argv=None):
     else:
         groups, ids, x = None, list(table.ids), table.on(dev)
     res = cluster.cluster(model, x, groups=groups, threshold=thr, min_clusters=args.min_clusters, linkage=args.linkage)
+    if args.vb_plda:
+        from neuralplda_amd import kaldi_format
+        psi = kaldi_format.read_plda(args.vb_plda)["Psi_across_covar_diag"]
+        res = cluster.vb_refine(model, x, res, psi, groups=groups, Fa=args.vb_fa, Fb=args.vb_fb, loop_prob=args.vb_loop,
+                                max_iters=args.vb_max_iters)
     s2u = res.spk2utt(ids, prefix=args.prefix)
     os.makedirs(args.out_dir, exist_ok=True)
     with open(os.path.join(args.out_dir, "spk2utt"), "w") as fh:
