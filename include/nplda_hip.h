@@ -872,6 +872,23 @@ int nplda_xvec_extract_f32(const float* x, int layout, int64_t ld_in, const int6
                            int64_t total_frames, int pooling, const void* packed, float* out, int64_t ldx, void* ws,
                            size_t ws_bytes, nplda_stream_t stream);
 
+/* Sliding-window extraction (design/k23_sliding_windows.md): x-vectors of n_windows row ranges of ONE dense pass over
+ * x, for diarization.  Workspace of one call: the dense buffers of total_frames frames plus 3008 floats per window,
+ * rounded to whole tiles (the same formula as nplda_xvec_workspace_bytes(total_frames, n_windows)). */
+size_t nplda_xvec_windows_workspace_bytes(int64_t total_frames, int64_t n_windows);
+/* out[w, 0:512] = extract(rows [win_begin[w], win_end[w]) of x as one utterance) for w < n_windows, bit for bit what
+ * nplda_xvec_extract_f32 gives for a copy of those rows.  x: (total_frames, ld_in) rows (NPLDA_XVEC_LAYOUT_ROWS only);
+ * win_begin, win_end: int64 device arrays of row indices into x.  The caller promises that the rows of a window are
+ * consecutive frames of one recording; windows may overlap, repeat and come in any order.  tdnn1..tdnn10 run ONCE over
+ * the total_frames rows, whatever the windows cover; a pooling kernel then takes, per window, the dense tdnn10 rows
+ * [begin, end - 22): fp64 sum in row order, mean, fp64 sum of squared deviations in row order, unbiased std or var (NaN
+ * at one pooled row), as the utterance pooling does; lin11 runs over the n_windows pooled rows.  Indices are clamped to
+ * [0, total_frames]; a window with end - begin <= 22 after clamping yields NaN pooled values (a NaN x-vector) and reads
+ * no row.  out: (n_windows, ldx), ldx >= 512, ldx % 4 == 0.  n_windows == 0 returns NPLDA_OK and touches nothing. */
+int nplda_xvec_extract_windows_f32(const float* x, int64_t ld_in, int64_t total_frames, const int64_t* win_begin,
+                                   const int64_t* win_end, int64_t n_windows, int pooling, const void* packed, float* out,
+                                   int64_t ldx, void* ws, size_t ws_bytes, nplda_stream_t stream);
+
 /* Training forward and backward of the same extractor (csrc/nplda_xvec_bwd.hip), for fine-tuning it end to end under
  * Etdnn_Xvec_NeuralPlda.train1() (utils/models.py:238-249: the tdnn batch norms on their running statistics).  Bytes of
  * the `saved` buffer of one nplda_xvec_extract_train_f32 call: the padded input image, every tdnn layer's normalised

@@ -234,6 +234,9 @@ SIGNATURES = {
     "nplda_xvec_workspace_bytes": (_c_sz, [_c_i64, _c_i64]),
     "nplda_xvec_extract_f32": (_c_int, [_c_f32p, _c_int, _c_i64, _c_vp, _c_i64, _c_i64, _c_int, _c_vp, _c_f32p, _c_i64, _c_vp,
                                         _c_sz, _c_vp]),
+    "nplda_xvec_windows_workspace_bytes": (_c_sz, [_c_i64, _c_i64]),
+    "nplda_xvec_extract_windows_f32": (_c_int, [_c_f32p, _c_i64, _c_i64, _c_vp, _c_vp, _c_i64, _c_int, _c_vp, _c_f32p, _c_i64,
+                                                _c_vp, _c_sz, _c_vp]),
     "nplda_xvec_train_saved_bytes": (_c_sz, [_c_i64, _c_i64]),
     "nplda_xvec_extract_train_f32": (_c_int, [_c_f32p, _c_int, _c_i64, _c_vp, _c_i64, _c_i64, _c_int, _c_vp, _c_f32p,
                                               _c_i64, _c_vp, _c_sz, _c_vp]),

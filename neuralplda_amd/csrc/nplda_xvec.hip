@@ -20,6 +20,8 @@
 //  * xvec_pool_kernel     statistics pooling (utils/models.py:152-156): per utterance and feature, mean and unbiased
 //                         std / var over the T_u - 22 valid tdnn10 rows, two passes with fp64 sums, one thread per
 //                         feature (fixed order: deterministic).
+//  * xvec_pool_windows_kernel  the same pooling over a table of (overlapping) row windows of ONE dense pass: sliding-window
+//                         x-vectors without running a frame through the layers once per window (design/k23).
 // The GEMM body, xvec_prep_kernel and xvec_pool_kernel live in nplda_xvec_body.h, shared with the training forward and
 // backward (nplda_xvec_bwd.hip).
 #include "nplda_xvec_body.h"
@@ -96,6 +98,99 @@ int launch_layer(int l, const float* packed, const float* in, long long ld_in, l
     return nplda_launch_status();
 }
 
+constexpr int kPoolLd = 16 * ((kPoolDim + 15) / 16);  // row stride of the tdnn10 output
+
+// lin11 over the n pooled rows (prows of them allocated: whole tiles, the padding rows zeroed)
+int lin11(const float* P, float* pooled, long long n, long long prows, float* out, long long ldx, hipStream_t st) {
+    if (prows > n && hipMemsetAsync(pooled + n * kPooledLd, 0, (size_t)(prows - n) * kPooledLd * 4, st) != hipSuccess)
+        return NPLDA_EINVAL;
+    return launch_layer(kTdnn, P, pooled, kPooledLd, prows, out, ldx, n, st);
+}
+
+// Prep and tdnn1..tdnn10 over total_frames rows: the common part of both extraction entry points.  Leaves the dense
+// tdnn10 rows (ld 1504) in the workspace's B buffer and returns it in *h.
+int dense_pass(const float* x, int layout, long long ld_in, long long T, long long total_frames, const WsLayout& w,
+               char* base, const float* P, hipStream_t st, const float** h) {
+    float* b0 = (float*)(base + w.o0);
+    float* bA = (float*)(base + w.oA);
+    float* bB = (float*)(base + w.oB);
+    const long long n0 = w.rows * kFeatP;
+    hipLaunchKernelGGL(xvec_prep_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, x, layout, ld_in, T,
+                       total_frames, w.rows, b0);
+    if (int rc = nplda_launch_status()) return rc;
+    // the slack rows of the activation buffers are read by the last tile's context taps (results discarded): zeroed
+    const long long live = w.rows - kRowSlack;
+    if (hipMemsetAsync(bA + live * kEmbDim, 0, (size_t)kRowSlack * kEmbDim * 4, st) != hipSuccess ||
+        hipMemsetAsync(bB + live * kEmbDim, 0, (size_t)kRowSlack * kEmbDim * 4, st) != hipSuccess ||
+        hipMemsetAsync(bB + live * kPoolLd, 0, (size_t)kRowSlack * kPoolLd * 4, st) != hipSuccess)
+        return NPLDA_EINVAL;
+    const float* in = b0;
+    long long ld = kFeatP;
+    for (int l = 0; l < kTdnn; ++l) {
+        float* o = (l & 1) ? bB : bA;
+        const long long ldo = l == kTdnn - 1 ? kPoolLd : kEmbDim;
+        if (int rc = launch_layer(l, P, in, ld, live, o, ldo, live, st)) return rc;
+        in = o;
+        ld = ldo;
+    }
+    *h = bB;
+    return NPLDA_OK;
+}
+
+// Statistics pooling over a table of row windows: window w pools the dense tdnn10 rows [begin[w], end[w] - 22), the
+// value xvec_pool_kernel gives for the same rows as an utterance, bit for bit (every column is one sequential fp64 chain
+// in row order, twice; nothing is reduced across threads).  One thread owns FOUR adjacent columns: a row is one 16-byte
+// load per lane (the rows are 16-byte aligned: ld 1504) and the four chains run interleaved, which hides the latency of
+// the dependent fp64 adds that the one-column mapping waits on.  128 threads per block, 3 blocks per window (375 column
+// quads).  The second pass re-reads rows this block has just read (128 x 16 B per row: they come back from the cache).
+constexpr int kWinPoolThreads = 128;
+constexpr int kWinPoolBlocks = (kPoolLd / 4 + kWinPoolThreads - 1) / kWinPoolThreads;
+
+__global__ __launch_bounds__(kWinPoolThreads) void xvec_pool_windows_kernel(const float* __restrict__ h,
+                                                                            const int64_t* __restrict__ begin,
+                                                                            const int64_t* __restrict__ end, long long R,
+                                                                            int pooling, float* __restrict__ pooled) {
+    const long long w = blockIdx.x / kWinPoolBlocks;
+    const int cb = (int)(blockIdx.x - w * kWinPoolBlocks), c4 = cb * kWinPoolThreads + threadIdx.x;
+    float* prow = pooled + w * kPooledLd;
+    if (cb == 0 && threadIdx.x < kPooledLd - 2 * kPoolDim) prow[2 * kPoolDim + threadIdx.x] = 0.f;
+    if (c4 >= kPoolDim / 4) return;  // 1500 = 4 x 375: no quad straddles the last column
+    long long b = begin[w], e = end[w];  // clamped as xvec_pool_kernel clamps a bad offset table
+    b = b < 0 ? 0 : (b > R ? R : b);
+    e = e < b ? b : (e > R ? R : e);
+    const long long n = e - b - kContext;
+    const f32x4* p = reinterpret_cast<const f32x4*>(h + b * kPoolLd) + c4;
+    constexpr long long ld4 = kPoolLd / 4;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+    for (long long t = 0; t < n; ++t) {
+        const f32x4 v = p[t * ld4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s[i] += (double)v[i];
+    }
+    double mean[4], q[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) mean[i] = n > 0 ? s[i] / (double)n : __builtin_nan("");
+#pragma unroll 4
+    for (long long t = 0; t < n; ++t) {
+        const f32x4 v = p[t * ld4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const double dv = (double)v[i] - mean[i];
+            q[i] += dv * dv;
+        }
+    }
+    f32x4 om, os;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const double var = n > 1 ? q[i] / (double)(n - 1) : __builtin_nan("");  // unbiased: NaN at n = 1
+        om[i] = (float)mean[i];
+        os[i] = (float)(pooling == NPLDA_XVEC_POOL_VAR ? var : sqrt(var));
+    }
+    *reinterpret_cast<f32x4*>(prow + 4 * c4) = om;
+    *reinterpret_cast<f32x4*>(prow + kPoolDim + 4 * c4) = os;
+}
+
 }  // namespace
 
 extern "C" {
@@ -153,39 +248,44 @@ int nplda_xvec_extract_f32(const float* x, int layout, int64_t ld_in, const int6
     if (ws_bytes < w.total) return NPLDA_ENOSPC;
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)ws;
-    float* b0 = (float*)(base + w.o0);
-    float* bA = (float*)(base + w.oA);
-    float* bB = (float*)(base + w.oB);
     float* pooled = (float*)(base + w.oP);
     const float* P = (const float*)packed;
     const long long T = layout == NPLDA_XVEC_LAYOUT_BCT ? total_frames / n_utts : 0;
-    const long long n0 = w.rows * kFeatP;
-    hipLaunchKernelGGL(xvec_prep_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, x, layout,
-                       (long long)ld_in, T, (long long)total_frames, w.rows, b0);
+    const float* h;
+    if (int rc = dense_pass(x, layout, ld_in, T, total_frames, w, base, P, st, &h)) return rc;
+    hipLaunchKernelGGL(xvec_pool_kernel, dim3((unsigned)(n_utts * kPoolBlocks)), dim3(256), 0, st, h,
+                       (long long)kPoolLd, offsets, (long long)total_frames, pooling, pooled);
     if (int rc = nplda_launch_status()) return rc;
-    // the slack rows of the activation buffers are read by the last tile's context taps (results discarded): zeroed
-    const long long live = w.rows - kRowSlack;
-    const int ldB = 16 * ((kPoolDim + 15) / 16);
-    if (hipMemsetAsync(bA + live * kEmbDim, 0, (size_t)kRowSlack * kEmbDim * 4, st) != hipSuccess ||
-        hipMemsetAsync(bB + live * kEmbDim, 0, (size_t)kRowSlack * kEmbDim * 4, st) != hipSuccess ||
-        hipMemsetAsync(bB + live * ldB, 0, (size_t)kRowSlack * ldB * 4, st) != hipSuccess)
+    return lin11(P, pooled, n_utts, w.urows, out, ldx, st);
+}
+
+size_t nplda_xvec_windows_workspace_bytes(int64_t total_frames, int64_t n_windows) {
+    if (total_frames < 0 || n_windows < 0) return 0;
+    return ws_layout(total_frames, n_windows).total;
+}
+
+int nplda_xvec_extract_windows_f32(const float* x, int64_t ld_in, int64_t total_frames, const int64_t* win_begin,
+                                   const int64_t* win_end, int64_t n_windows, int pooling, const void* packed, float* out,
+                                   int64_t ldx, void* ws, size_t ws_bytes, nplda_stream_t stream) {
+    if (n_windows < 0 || total_frames < 0) return NPLDA_EINVAL;
+    if (pooling != NPLDA_XVEC_POOL_STD && pooling != NPLDA_XVEC_POOL_VAR) return NPLDA_EINVAL;
+    if (n_windows == 0) return NPLDA_OK;
+    if (!x || !win_begin || !win_end || !packed || !out || !ws || !nplda_aligned16(packed) || !nplda_aligned16(out) ||
+        !nplda_aligned16(ws) || ldx < kEmbDim || (ldx % 4) != 0 || ld_in < kFeat)
         return NPLDA_EINVAL;
-    const float* in = b0;
-    long long ld = kFeatP;
-    for (int l = 0; l < kTdnn; ++l) {
-        float* o = (l & 1) ? bB : bA;
-        const long long ldo = l == kTdnn - 1 ? ldB : kEmbDim;
-        if (int rc = launch_layer(l, P, in, ld, live, o, ldo, live, st)) return rc;
-        in = o;
-        ld = ldo;
-    }
-    hipLaunchKernelGGL(xvec_pool_kernel, dim3((unsigned)(n_utts * kPoolBlocks)), dim3(256), 0, st, bB,
-                       (long long)ldB, offsets, (long long)total_frames, pooling, pooled);
+    if (n_windows > 0x7fffffffLL / kWinPoolBlocks) return NPLDA_EUNSUPPORTED;
+    const WsLayout w = ws_layout(total_frames, n_windows);
+    if (ws_bytes < w.total) return NPLDA_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)ws;
+    float* pooled = (float*)(base + w.oP);
+    const float* P = (const float*)packed;
+    const float* h;
+    if (int rc = dense_pass(x, NPLDA_XVEC_LAYOUT_ROWS, ld_in, 0, total_frames, w, base, P, st, &h)) return rc;
+    hipLaunchKernelGGL(xvec_pool_windows_kernel, dim3((unsigned)(n_windows * kWinPoolBlocks)), dim3(kWinPoolThreads), 0,
+                       st, h, win_begin, win_end, (long long)total_frames, pooling, pooled);
     if (int rc = nplda_launch_status()) return rc;
-    if (w.urows > n_utts &&
-        hipMemsetAsync(pooled + n_utts * kPooledLd, 0, (size_t)(w.urows - n_utts) * kPooledLd * 4, st) != hipSuccess)
-        return NPLDA_EINVAL;
-    return launch_layer(kTdnn, P, pooled, kPooledLd, w.urows, out, ldx, n_utts, st);
+    return lin11(P, pooled, n_windows, w.urows, out, ldx, st);
 }
 
 }  // extern "C"

@@ -6,6 +6,8 @@ hand-written HIP (csrc/nplda_xvec.hip through include/nplda_hip.h):
 
     extract(x)                     (B, 30, T) features -> (B, 512) x-vectors                 (utils/models.py:170-186)
     extract_ragged(frames, lens)   (sum T_u, 30) frames of utterances of different lengths -> (U, 512)
+    extract_windows(frames, wins)  (R, 30) frames and (W, 2) [begin, end) row windows -> (W, 512): sliding-window x-vectors
+                                   from one dense pass, bit for bit extract_ragged on the cut-outs (design/k23)
     extract_from_scp(feats_scp)    a Kaldi feature scp (+ VAD) -> keys, (U, 512): features.py's front end, then extract_ragged
     Etdnn_Xvec_NeuralPlda.forward  extract both sides, then the existing HIP NPLDA head       (utils/models.py:251-268)
 
@@ -34,7 +36,8 @@ import torch.nn as nn
 from . import _lib, features, kaldi_format
 from .models import NeuralPlda, _compute_device
 
-__all__ = ["TDNN", "XVectorNet_ETDNN_12Layer", "Etdnn_Xvec_NeuralPlda", "LAYERS", "CONTEXT", "flops_per_frame"]
+__all__ = ["TDNN", "XVectorNet_ETDNN_12Layer", "Etdnn_Xvec_NeuralPlda", "LAYERS", "CONTEXT", "flops_per_frame",
+           "plan_windows", "WindowChunk"]
 
 # (Din, Dout, context, dilation) of tdnn1..tdnn10 (utils/models.py:104-123)
 LAYERS = ((30, 512, 5, 1), (512, 512, 1, 1), (512, 512, 3, 2), (512, 512, 1, 1), (512, 512, 3, 3), (512, 512, 1, 1),
@@ -74,6 +77,55 @@ def _chunks(lengths, limit):
     if u0 < len(lengths):
         out.append((u0, len(lengths)))
     return out
+
+
+class WindowChunk:
+    """One extraction call of plan_windows: `windows` (indices into the caller's table, in order of begin), `intervals`
+    ([(b, e)] disjoint ascending runs of the caller's rows: the union of the windows' rows, laid end to end as the call's
+    input), `begin` / `end` (int64 rows of each window inside that input) and `rows` (input rows)."""
+
+    def __init__(self, windows, intervals, begin, end):
+        self.windows, self.intervals, self.begin, self.end = windows, intervals, begin, end
+        self.rows = int(sum(e - b for b, e in intervals))
+
+
+def plan_windows(windows, limit):
+    """Split a (W, 2) table of [begin, end) row windows into extraction calls whose workspace stays within `limit` bytes
+    (a window that does not fit on its own still runs alone) -> [WindowChunk].  The windows are taken in order of begin.
+    A call's input is the union of its windows' rows: rows that no window covers are never run through the layers, and
+    a cut between two calls recomputes only the rows that windows on both sides of it cover.  A window pools only rows
+    whose context lies inside its own rows, so neither the laying end to end nor a cut changes a bit of the result."""
+    win = np.asarray(windows, dtype=np.int64).reshape(-1, 2)
+    order = np.lexsort((win[:, 1], win[:, 0]))
+    B, E = win[order, 0], win[order, 1]
+    W, s, chunks = order.size, 0, []
+    while s < W:
+        K = 64  # windows looked at: grown until the cut (or the table's end) lies inside
+        while True:
+            hi = min(s + K, W)
+            b, e = B[s:hi], E[s:hi]
+            top = np.maximum.accumulate(e)
+            prev = np.concatenate([b[:1], top[:-1]])  # where the union of the windows before this one ends
+            new = b > prev                            # a gap in front: the window opens an interval
+            new[0] = True
+            rows = np.cumsum(np.where(new, e - b, np.maximum(e - prev, 0)))
+            over = _ws_bytes(rows, np.arange(1, hi - s + 1)) > limit
+            over[0] = False
+            if over.any():
+                n = int(np.argmax(over))
+                break
+            if hi == W:
+                n = hi - s
+                break
+            K *= 4
+        first = np.flatnonzero(new[:n])
+        last = np.concatenate([first[1:], [n]]) - 1   # the last window of each interval
+        iv = np.cumsum(new[:n]) - 1                   # each window's interval
+        iv_end, iv_rows = top[last][iv], rows[last][iv]
+        chunks.append(WindowChunk(order[s:s + n], list(zip(b[first].tolist(), top[last].tolist())),
+                                  iv_rows - (iv_end - b[:n]), iv_rows - (iv_end - e[:n])))
+        s += n
+    return chunks
 
 
 def _pool_kind(fn):
@@ -300,6 +352,64 @@ class XVectorNet_ETDNN_12Layer(nn.Module):
             out = _ExtractFn.apply(self, X, LAYOUT_ROWS, lengths, dev, *self._grad_params())
         else:
             out = self._run(X, LAYOUT_ROWS, lengths, dev, workspace_bytes)
+        return out if out.device == frames.device else out.to(frames.device)
+
+    def extract_windows(self, frames, windows, workspace_bytes=None):
+        """Sliding-window x-vectors: frames (R, 30) rows, windows (W, 2) integer [begin, end) rows (array, tensor or list;
+        they may overlap, repeat and come in any order; the rows of a window are consecutive frames of one recording) ->
+        (W, 512) in the caller's window order.  Row w is bit for bit extract_ragged(frames[begin:end], [end - begin]), but
+        every covered frame runs through tdnn1..tdnn10 once per call, not once per window (nplda_xvec_extract_windows_f32).
+        A table whose workspace exceeds workspace_bytes (default MAX_WORKSPACE_BYTES) is worked through in order of begin
+        by plan_windows, which does not change a bit.  Inference only."""
+        if frames.dim() != 2 or frames.shape[1] != FEAT:
+            raise ValueError(f"extract_windows expects (frames, {FEAT}) rows, got {tuple(frames.shape)}")
+        win = np.asarray(windows.cpu() if isinstance(windows, torch.Tensor) else windows)
+        if win.size == 0:
+            win = np.zeros((0, 2), np.int64)
+        if win.ndim != 2 or win.shape[1] != 2 or win.dtype.kind not in "iu":
+            raise ValueError(f"windows must be (W, 2) integer [begin, end) rows, got {win.dtype} {win.shape}")
+        win = win.astype(np.int64)
+        R, W = int(frames.shape[0]), int(win.shape[0])
+        bad = np.flatnonzero((win[:, 0] < 0) | (win[:, 1] > R))
+        if bad.size:
+            w = int(bad[0])
+            raise ValueError(f"window {w} = [{win[w, 0]}, {win[w, 1]}) lies outside the {R} rows of frames")
+        short = np.flatnonzero(win[:, 1] - win[:, 0] <= CONTEXT)
+        if short.size:
+            w = int(short[0])
+            raise ValueError(f"window {w} = [{win[w, 0]}, {win[w, 1]}) has {win[w, 1] - win[w, 0]} frames, shorter than the "
+                             f"extractor's context ({CONTEXT + 1} frames at least)")
+        self._check_mode(frames)  # (no training path here: a trainable extractor under grad mode is an error)
+        dev = _compute_device(frames, self.lin11.weight)
+        out = torch.empty((W, XVEC_DIM), dtype=torch.float32, device=dev)
+        if W:
+            X = frames.detach().to(dev, torch.float32).contiguous()
+            packed = self._packed(dev)
+            kind = _pool_kind(self.pooling_function)
+            lib = _lib.load()
+            limit = MAX_WORKSPACE_BYTES if workspace_bytes is None else int(workspace_bytes)
+            with _lib.on_device(dev):
+                st = _lib.current_stream(dev)
+                w0 = 0
+                order = []
+                for ch in plan_windows(win, limit):
+                    n = len(ch.windows)
+                    src = (X[ch.intervals[0][0]:ch.intervals[0][1]] if len(ch.intervals) == 1
+                           else torch.cat([X[b:e] for b, e in ch.intervals]))
+                    tab = torch.from_numpy(np.stack([ch.begin, ch.end])).to(dev)
+                    ws_n = lib.nplda_xvec_windows_workspace_bytes(ch.rows, n)
+                    ws = torch.empty(ws_n, dtype=torch.uint8, device=dev)
+                    _lib.check(lib.nplda_xvec_extract_windows_f32(src.data_ptr(), FEAT, ch.rows, tab[0].data_ptr(),
+                                                                  tab[1].data_ptr(), n, kind, packed.data_ptr(),
+                                                                  out[w0:w0 + n].data_ptr(), XVEC_DIM, ws.data_ptr(), ws_n,
+                                                                  st), "nplda_xvec_extract_windows_f32")
+                    order.append(ch.windows)
+                    w0 += n
+                order = np.concatenate(order)
+                if not np.array_equal(order, np.arange(W)):  # rows came out in order of begin: back to the caller's
+                    inv = np.empty(W, np.int64)
+                    inv[order] = np.arange(W)
+                    out = out.index_select(0, torch.from_numpy(inv).to(dev))
         return out if out.device == frames.device else out.to(frames.device)
 
     def extract_from_scp(self, feats_scp, vad=features.VadOptions(), cmn_window=300, min_frames=25, utts_per_call=2048,
