@@ -1101,6 +1101,62 @@ int nplda_vbhmm_f64(const float* z, int64_t ldz, const int64_t* offsets_host, co
                     double* elbo, int32_t* n_iters, int32_t* labels, int32_t* n_speakers, void* ws, size_t ws_bytes,
                     nplda_stream_t stream);
 
+/* ---- diarization error rate with the optimal speaker mapping -------------------------------------------------- */
+
+/* csrc/nplda_der.hip, design/k24_der.md.  One call scores P PROBLEMS against Rn RECORDINGS; a problem names a recording
+ * (prob_reco) and holds one hypothesis for it, and many problems may share a recording: the reference side is prepared once
+ * per recording.  Everything counts in integer frames and every output is an exact integer; there is no floating point.
+ *
+ * Recording r has T_r = frame_offsets[r + 1] - frame_offsets[r] frames.  A TURN is three int32 (begin, end, speaker) with
+ * 0 <= begin <= end <= T_r and a speaker local to the recording and to its side, in [0, n_ref_speakers) for the reference
+ * and [0, n_hyp_speakers) for a hypothesis (both at most nplda_der_max_speakers()).  Turns may overlap, on both sides, and
+ * the turns of one speaker are taken as given.  The reference turns of recording r are the rows ref_offsets[r] ..
+ * ref_offsets[r + 1] of ref_turns.  On the device the bounds of a turn are clamped to [0, T_r]; a turn whose end lies before
+ * its begin, or whose speaker is outside the limit, does not exist (it has no collar either).
+ *
+ * SCORED frames of a recording: the frames inside its UEM regions (rows uem_offsets[r] .. uem_offsets[r + 1] of uem, two
+ * int32 (begin, end) each; uem_offsets == NULL: [0, T_r) for every recording; a recording without a region has no scored
+ * frame), less every frame f with b - collar <= f < b + collar or e - collar <= f < e + collar for a reference turn [b, e),
+ * less, with skip_overlap != 0, every frame with more than one reference speaker.
+ *
+ * HYPOTHESES, exactly one of two forms per call (the other form's pointers all NULL):
+ *   turns:          hyp_offsets (P + 1) into hyp_turns, the rows of a problem as for the reference;
+ *   labelled items: frame_item holds one int32 per frame of every RECORDING (at frame_offsets[r] + f), the index of the item
+ *                   (window) that owns the frame or -1; item_offsets (P + 1) into item_labels, one int32 label per item of
+ *                   the PROBLEM in [0, n_hyp_speakers) or -1 for no speaker.  An item index outside the problem's items and a
+ *                   label outside the limit count as -1.
+ *
+ * With R(t), H(t) the sets of active reference and hypothesis speakers at a scored frame t, per problem:
+ *   counts[6] (int64): scored = the number of scored frames, total = sum |R|, miss = sum max(0, |R| - |H|),
+ *                      fa = sum max(0, |H| - |R|), summin = sum min(|R|, |H|), matched = max over one-to-one partial
+ *                      mappings m of sum_i C[i][m(i)], where C[i][j] = scored frames with i in R(t) and j in H(t);
+ *                      speaker confusion is summin - matched and DER = (miss + fa + summin - matched) / total;
+ *   map_ref[64] (int32): the hypothesis speaker of each reference speaker under one optimal mapping, -1 for a speaker that
+ *                      is unmapped or shares no scored frame with its partner.  Ties between optimal mappings are broken by a
+ *                      fixed rule (rows enter the shortest-augmenting-path search in increasing order, the lowest column
+ *                      among equal smallest slacks is taken), so the mapping is a function of C alone;
+ *   C[64 * 64] (int32, row = reference speaker), or C == NULL.
+ * A problem of an empty recording gets zeros and -1.
+ *
+ * The offset tables and prob_reco are given on the host (read during the call only: checks and sizes) and on the device.
+ * NPLDA_EINVAL: a negative count, collar or speaker limit, offsets that do not start at 0 or decrease, prob_reco_host
+ * outside [0, Rn), both or neither hypothesis form, a null or misaligned pointer (int64 tables and counts 8 bytes, int32
+ * tables 4, ws 16).  NPLDA_EUNSUPPORTED: a speaker limit above nplda_der_max_speakers(), T_r above 2^31 - 1, more than 2^40
+ * frames, Rn or P above 2^24.  NPLDA_ENOSPC: ws_bytes below nplda_der_workspace_bytes(frame_offsets_host, Rn) (0 where the
+ * offsets are not acceptable, else a positive multiple of 256: 12 bytes per frame).  Caller-owned workspace, nothing
+ * allocated, no host synchronisation, capturable, the same bits on every call, integer atomics only (OR on the frame
+ * masks, ADD on C in LDS: order-free), nothing read back; P == 0 is a no-op; every error is a status code before any launch. */
+int nplda_der_max_speakers(void); /* 64: a speaker per bit of a frame's mask and per lane in the assignment */
+int nplda_der_block(void);        /* threads of the counting workgroup (one workgroup per problem) */
+size_t nplda_der_workspace_bytes(const int64_t* frame_offsets_host, int64_t Rn);
+int nplda_der_i64(const int64_t* frame_offsets_host, const int64_t* frame_offsets, int64_t Rn, const int64_t* ref_offsets_host,
+                  const int64_t* ref_offsets, const int32_t* ref_turns, const int64_t* uem_offsets_host, const int64_t* uem_offsets,
+                  const int32_t* uem, int collar, int skip_overlap, int n_ref_speakers, int n_hyp_speakers,
+                  const int32_t* prob_reco_host, const int32_t* prob_reco, int64_t P, const int64_t* hyp_offsets_host,
+                  const int64_t* hyp_offsets, const int32_t* hyp_turns, const int32_t* frame_item, const int64_t* item_offsets_host,
+                  const int64_t* item_offsets, const int32_t* item_labels, int64_t* counts, int32_t* map_ref, int32_t* C, void* ws,
+                  size_t ws_bytes, nplda_stream_t stream);
+
 /* ---- measurement utility ------------------------------------------------------------------------------------- */
 
 /* Shader-clock probe for bench.py (no reference counterpart): one wave that stays resident for window_us microseconds

@@ -202,6 +202,11 @@ SIGNATURES = {
     "nplda_vbhmm_workspace_bytes": (_c_sz, [_c_vp, _c_vp, _c_i64, _c_int]),
     "nplda_vbhmm_f64": (_c_int, [_c_f32p, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_vp, _c_vp] +
                         [ctypes.c_double] * 5 + [_c_int] + [_c_vp] * 7 + [_c_sz, _c_vp]),
+    "nplda_der_max_speakers": (_c_int, []),
+    "nplda_der_block": (_c_int, []),
+    "nplda_der_workspace_bytes": (_c_sz, [_c_vp, _c_i64]),
+    "nplda_der_i64": (_c_int, [_c_vp, _c_vp, _c_i64] + [_c_vp] * 6 + [_c_int] * 4 + [_c_vp, _c_vp, _c_i64] + [_c_vp] * 11 +
+                      [_c_sz, _c_vp]),
     "nplda_matrix_frag_bytes": (_c_sz, [_c_int, _c_int]),
     "nplda_pack_matrix_f32": (_c_int, [_c_f32p, _c_i64, _c_int, _c_int, _c_int, _c_vp, _c_sz, _c_vp]),
     "nplda_dplda_quadform_f32": (_c_int, [_c_f32p, _c_int, _c_vp, _c_sz, _c_f32p, _c_vp]),

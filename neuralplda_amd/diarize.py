@@ -10,8 +10,15 @@
                                           cluster.vb_refine -> turns
 
 Everything here counts in frames, local to a recording; seconds appear only where a file holds them (frame_shift,
-0.01 s by default).  A recording's segments do not overlap.  No DER scoring, no overlap detection, no RTTM reader
-(design/k23_sliding_windows.md).
+0.01 s by default).  A recording's segments do not overlap.  No overlap detection (design/k23_sliding_windows.md).
+
+Scoring (design/k24_der.md; the rate itself is metrics.der):
+
+    read_rttm(path, frame_shift)          the SPEAKER lines of an RTTM file -> (reco_ids, (N, 4) turns, speaker names)
+    read_uem(path, frame_shift)           a UEM file -> (reco_ids, per recording (n, 2) regions)
+    Diarization.der(ref_turns, ...)       the DER of the result's own turns
+    sweep_thresholds(diarization, ref_turns, thresholds, ...)   the DER of every cut of the recorded dendrogram, all
+                                          (threshold, recording) cells in ONE device call
 """
 import numpy as np
 import torch
@@ -20,7 +27,7 @@ from . import cluster, features
 from .xvector import CONTEXT
 
 __all__ = ["speech_segments", "read_segments", "uniform_windows", "frame_labels", "turns", "write_rttm", "diarize",
-           "Diarization"]
+           "Diarization", "read_rttm", "read_uem", "sweep_thresholds", "SweepResult"]
 
 FRAME_SHIFT = 0.01
 
@@ -175,6 +182,65 @@ def write_rttm(path_or_fh, reco_ids, turns, frame_shift=FRAME_SHIFT):
             f.write(text)
 
 
+def read_rttm(path, frame_shift=FRAME_SHIFT):
+    """The `SPEAKER <recording> <channel> <start> <duration> <NA> <NA> <speaker> ...` lines of an RTTM file (other line
+    types and `;` comments are passed over) -> (reco_ids in order of first appearance, turns: (N, 4) int64 rows (recording
+    index, begin, end, label) in the order of turns(): by recording, begin, end, speaker_names: per recording the names in
+    order of first appearance in the file; a label indexes its recording's names).  Times are round(t / frame_shift)
+    frames, begin from <start> and end from <start> + <duration>."""
+    recs, index, names, rows = [], {}, [], []
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            p = line.split()
+            if not p or p[0].startswith(";") or p[0] != "SPEAKER":
+                continue
+            if len(p) < 8:
+                raise ValueError(f"{path}:{ln}: expected `SPEAKER <recording> <channel> <start> <duration> <NA> <NA> <speaker>`")
+            try:
+                start, dur = float(p[3]), float(p[4])
+            except ValueError:
+                raise ValueError(f"{path}:{ln}: start {p[3]!r} and duration {p[4]!r} must be numbers") from None
+            b, e = int(round(start / frame_shift)), int(round((start + dur) / frame_shift))
+            if not (start >= 0.0 and dur >= 0.0) or e < b:
+                raise ValueError(f"{path}:{ln}: a turn of {p[7]} starts at {p[3]} and lasts {p[4]}")
+            if p[1] not in index:
+                index[p[1]] = len(recs)
+                recs.append(p[1])
+                names.append([])
+            r = index[p[1]]
+            if p[7] not in names[r]:
+                names[r].append(p[7])
+            rows.append((r, b, e, names[r].index(p[7])))
+    rows.sort(key=lambda t: (t[0], t[1], t[2]))
+    return recs, np.array(rows, np.int64).reshape(-1, 4), names
+
+
+def read_uem(path, frame_shift=FRAME_SHIFT):
+    """A UEM file (`<recording> <channel> <start> <end>`, seconds; `;` comments) -> (reco_ids in order of first
+    appearance, per recording an (n, 2) int64 array of [begin, end) regions sorted by begin, times as
+    round(t / frame_shift) frames)."""
+    recs, rows = [], {}
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            p = line.split()
+            if not p or p[0].startswith(";"):
+                continue
+            try:
+                if len(p) < 4:
+                    raise ValueError
+                start, end = float(p[2]), float(p[3])
+            except ValueError:
+                raise ValueError(f"{path}:{ln}: expected `<recording> <channel> <start> <end>`") from None
+            b, e = int(round(start / frame_shift)), int(round(end / frame_shift))
+            if not start >= 0.0 or e < b:
+                raise ValueError(f"{path}:{ln}: a region of {p[0]} runs from {p[2]} to {p[3]}")
+            if p[0] not in rows:
+                recs.append(p[0])
+                rows[p[0]] = []
+            rows[p[0]].append((b, e))
+    return recs, [np.array(sorted(rows[r]), np.int64).reshape(-1, 2) for r in recs]
+
+
 class Diarization:
     """The result of diarize(): `reco_ids`, `segments` (as speech_segments), `windows` ((W, 4): recording, segment,
     begin, end), `dropped` (segments too short for a window), `xvectors` ((W, 512) on the device), `labels` ((W,) int64,
@@ -187,6 +253,106 @@ class Diarization:
 
     def write_rttm(self, path_or_fh, frame_shift=FRAME_SHIFT):
         write_rttm(path_or_fh, self.reco_ids, self.turns, frame_shift)
+
+    def der(self, ref_turns, **kw):
+        """metrics.der of the result's own turns against ref_turns (whatever metrics.der takes as `ref`; the recording index of
+        bare turns names self.reco_ids); **kw: lengths, uem, collar, skip_overlap, frame_shift."""
+        from . import metrics
+        return metrics.der(ref_turns, self.turns, reco_ids=self.reco_ids, **kw)
+
+
+class SweepResult:
+    """What sweep_thresholds returns: `thresholds` (K,), `reco_ids` (R), `der` (K,) the pooled rate per threshold,
+    `per_recording` (K, R) (NaN: no reference speech, or the cell was not scored), `n_pooled` (K,) the recordings whose
+    counts `der` pools, `counts` (K, R, 6) int64 in the order of ops.DER_COUNTS (zeros where not scored) and
+    `best_threshold`: the one with the lowest pooled rate (the first of equal ones; None when every rate is NaN)."""
+
+    def __init__(self, thresholds, reco_ids, counts, scored):
+        from .derscore import rates
+        self.thresholds, self.reco_ids, self.counts = np.asarray(thresholds, np.float64), reco_ids, counts
+        conf = counts[..., 4] - counts[..., 5]
+        self.per_recording = rates(counts[..., 2], counts[..., 3], conf, counts[..., 1])
+        self.per_recording[~scored] = np.nan
+        self.n_pooled = scored.sum(axis=1).astype(np.int64)
+        self.der = rates(counts[..., 2].sum(axis=1), counts[..., 3].sum(axis=1), conf.sum(axis=1), counts[..., 1].sum(axis=1))
+        ok = ~np.isnan(self.der)
+        self.best_threshold = float(self.thresholds[np.flatnonzero(ok)[np.argmin(self.der[ok])]]) if ok.any() else None
+
+
+def sweep_thresholds(diarization, ref_turns, thresholds, reco_ids=None, lengths=None, uem=None, collar=0.25, skip_overlap=False,
+                     frame_shift=FRAME_SHIFT):
+    """The DER of every cut of a diarization's dendrogram -> SweepResult.  For each threshold t,
+    diarization.clustering.cut(t) (on the host) labels the windows; a cell (t, recording) is then exactly
+    metrics.der(ref_turns, turns(windows, those labels)) for that recording, but no turns are built: the device is given, once
+    per recording, the window that owns each frame (frame_labels' rule does not depend on the labels) and, per cell, one label
+    per window, and scores all K x R cells in ONE call.  ref_turns, lengths, uem, collar, skip_overlap: as metrics.der;
+    reco_ids: the names that the recording index of a bare ref_turns table refers to (default: the diarization's)
+    (recordings of the reference that the diarization does not have are scored against nothing, at every threshold).
+    A cell whose cut leaves the recording with more than 64 clusters is not scored: NaN, and its recording is left out of that
+    threshold's pool (SweepResult.n_pooled says how many went in); so is a recording with more than 64 reference speakers.
+    Raises where the recorded dendrogram does not reach a threshold: a recording whose clustering stopped early (threshold or
+    min_clusters of diarize()) must have recorded a merge below the lowest threshold asked for.  The VB-HMM is not part of the
+    sweep: the cells score the clustering's cuts, not `refined`."""
+    from . import derscore, ops
+    clus = diarization.clustering
+    thresholds = [float(t) for t in np.asarray(thresholds, np.float64).reshape(-1)]
+    if not thresholds or any(t != t for t in thresholds):
+        raise ValueError("give at least one threshold, none of them NaN")
+    win = np.asarray(diarization.windows, np.int64).reshape(-1, 4)
+    if win.shape[0] and (clus is None or len(clus) != win.shape[0]):
+        raise ValueError("the diarization carries no clustering of its windows")
+    if clus is not None:
+        n, mo = np.diff(clus.offsets), clus._moffs()
+        for p in np.flatnonzero(np.asarray(clus.n_merges) < np.maximum(n - 1, 0)).tolist():
+            done = clus.merges[mo[p]:mo[p] + int(clus.n_merges[p])]
+            if done.size == 0 or not float(done["value"].min()) < min(thresholds):
+                raise ValueError(f"the dendrogram of group {p} was recorded down to "
+                                 f"{float(done['value'].min()) if done.size else float('inf')}: it does not reach the threshold "
+                                 f"{min(thresholds)} (diarize with threshold=-inf, min_clusters=1 to record all of it)")
+    dev = derscore._device()
+    own = list(diarization.reco_ids)
+    rside, rorder = derscore._side(ref_turns, own if reco_ids is None else reco_ids, frame_shift, "ref_turns")
+    ids = derscore._recordings(own, rorder)
+    extent = {own[r]: int(win[win[:, 0] == r, 3].max()) for r in np.unique(win[:, 0]).tolist()}
+    R = derscore.Reference(rside, ids, derscore._lengths(lengths, own if reco_ids is None else reco_ids),
+                           derscore._uem(uem, frame_shift), collar, skip_overlap, frame_shift, extent, dev)
+    # the window that owns each frame, as an index into its recording's windows
+    rows_of = {r: np.flatnonzero(win[:, 0] == r) for r in np.unique(win[:, 0]).tolist()}
+    local = np.zeros(win.shape[0], np.int64)
+    for idx in rows_of.values():
+        local[idx] = np.arange(idx.size)
+    frame_item = np.full(R.frame_offsets.rows, -1, np.int32)
+    for r, _, b0, fl in frame_labels(win, np.arange(win.shape[0])):
+        if own[r] in R.index:
+            k = R.index[own[r]]
+            f0, T = int(R.frame_offsets.host[k]), int(R.frame_offsets.host[k + 1] - R.frame_offsets.host[k])
+            e = min(b0 + fl.size, T)  # (a given length may cut a recording short)
+            frame_item[f0 + b0:f0 + e] = np.where(fl[:e - b0] >= 0, local[np.maximum(fl[:e - b0], 0)], -1)
+    K, limit = len(thresholds), R.limit
+    counts = np.zeros((K, len(ids), len(ops.DER_COUNTS)), np.int64)
+    scored = np.zeros((K, len(ids)), bool)
+    prob, cells, labels, ioffs = [], [], [], [0]
+    cuts = [clus.cut(t).labels if clus is not None else np.zeros(0, np.int64) for t in thresholds]
+    for r, rid in enumerate(ids):  # a recording's cells side by side: their workgroups read the same reference masks
+        if rid not in R.index:
+            continue
+        idx = rows_of.get(r, np.zeros(0, np.int64)) if r < len(own) else np.zeros(0, np.int64)
+        for k in range(K):
+            u, inv = np.unique(cuts[k][idx], return_inverse=True)
+            if u.size > limit:
+                continue
+            prob.append(R.index[rid])
+            cells.append((k, r))
+            labels.append(inv.astype(np.int32).reshape(-1))
+            ioffs.append(ioffs[-1] + idx.size)
+    if prob:
+        got, _ = R.score(prob, frame_item=torch.from_numpy(frame_item).to(dev),
+                         item_offsets=ops.RaggedOffsets(ioffs, dev, max_rows=ops.DER_MAX_FRAMES),
+                         item_labels=torch.from_numpy(np.concatenate(labels)).to(dev))
+        kk, rr = np.array(cells).T
+        counts[kk, rr] = got
+        scored[kk, rr] = True
+    return SweepResult(thresholds, ids, counts, scored)
 
 
 def diarize(model, extractor, frames, lengths, reco_ids, segments=None, vad=features.VadOptions(), min_speech=50,

@@ -28,15 +28,21 @@ Confidence intervals (kernels nplda_bootstrap_*, csrc/nplda_bootstrap.hip, desig
 * bootstrap(scores, target, groups1, groups2): EER, min cost (and with llr=True actual cost and Cllr) of n_boot
   resamplings of the groups of both trial sides; bootstrap_ci: percentile intervals; bootstrap_diff: the paired
   comparison of two systems on the same trials under the same resamplings.
+
+Diarization (kernels of csrc/nplda_der.hip, design/k24_der.md; the host side is neuralplda_amd/derscore.py):
+
+* der(ref, hyp, ...): the diarization error rate of NIST md-eval on a frame grid, with the optimal speaker mapping, a
+  collar, optional exclusion of overlapped speech and UEM regions -> DerResult (exact integer counts per recording).
 """
 import math
 
 import torch
 
 from . import _lib, ops
+from .derscore import DerResult, der
 
 __all__ = ["minc", "eer", "minc_exact", "cllr", "act_cost", "act_dcf", "min_cllr", "rocch_eer", "rocch", "bootstrap",
-           "bootstrap_ci", "bootstrap_diff", "BootstrapResult"]
+           "bootstrap_ci", "bootstrap_diff", "BootstrapResult", "der", "DerResult"]
 
 
 def _on_device(output, target):

@@ -1250,18 +1250,22 @@ AHC_MERGE_DTYPE = [("a", "<i4"), ("b", "<i4"), ("value", "<f8"), ("size_after", 
 class RaggedOffsets:
     """The row offsets of P independent problems over one table, on the host (int64 numpy, what the C entry points check and
     size their launches by) and on a device (what the kernels read).  Make one outside a graph capture: building it copies
-    from the host."""
+    from the host.  max_rows: the most rows a problem may have (None: nplda_ahc_max_n(), what the clustering and the VB-HMM
+    take; ops.der lays its frames and turns out with larger ones)."""
 
     __slots__ = ("host", "dev", "P", "rows", "elems", "records")
 
-    def __init__(self, offsets, device):
+    def __init__(self, offsets, device, max_rows=None):
         import numpy as np
         host = np.ascontiguousarray(np.asarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets, dtype=np.int64))
         if host.ndim != 1 or host.size < 1 or host[0] != 0 or (np.diff(host) < 0).any():
             raise ValueError("offsets must be P + 1 non-decreasing row offsets that start at 0")
         lib = _lib.load()
         self.host, self.P, self.rows = host, host.size - 1, int(host[-1])
-        if self.P and int(np.diff(host).max()) > lib.nplda_ahc_max_n():
+        if max_rows is not None:
+            if self.P and int(np.diff(host).max()) > int(max_rows):
+                raise ValueError(f"a problem may have at most {int(max_rows)} rows")
+        elif self.P and int(np.diff(host).max()) > lib.nplda_ahc_max_n():
             raise ValueError(f"a problem may have at most {lib.nplda_ahc_max_n()} rows")
         n = np.diff(host)
         self.elems, self.records = int((n * n).sum()), int(np.maximum(n - 1, 0).sum())
@@ -1425,6 +1429,123 @@ def vbhmm(z, offsets, spk_offsets, psi, labels_init=None, gamma_init=None, pi_in
                                    _lib.current_stream())
     _lib.check(code, "nplda_vbhmm_f64")
     return gamma, pi, elbo, n_iters, labels, n_speakers
+
+
+DER_MAX_FRAMES = 2 ** 31 - 1  # frames per recording: turn bounds are int32
+DER_COUNTS = ("scored", "total", "miss", "fa", "summin", "matched")  # the columns of der()'s counts
+
+
+def _der_offsets(offsets, dev, name, P=None):
+    if not isinstance(offsets, RaggedOffsets):
+        offsets = RaggedOffsets(offsets, dev, max_rows=DER_MAX_FRAMES)
+    if offsets.dev.device != dev:
+        raise ValueError(f"{name} lives on another device")
+    if P is not None and offsets.P != P:
+        raise ValueError(f"{name} must hold {P} + 1 offsets, got {offsets.P} + 1")
+    return offsets
+
+
+def _der_table(t, rows, cols, name, dev):
+    t = torch.as_tensor(t)
+    if t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise TypeError(f"{name} must hold integers")
+    if tuple(t.shape) != ((rows, cols) if cols else (rows,)):
+        raise ValueError(f"{name} must be {(rows, cols) if cols else (rows,)}, got {tuple(t.shape)}")
+    return t.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def der_problems(prob_reco, device):
+    """The recording of each problem of der(), on the host and on the device -> the pair der() takes as prob_reco.  Make
+    one outside a graph capture: building it copies from the host."""
+    import numpy as np
+    host = np.ascontiguousarray(np.asarray(prob_reco.cpu() if isinstance(prob_reco, torch.Tensor) else prob_reco,
+                                           dtype=np.int64).astype(np.int32))
+    if host.ndim != 1:
+        raise ValueError("prob_reco must name one recording per problem")
+    return host, torch.from_numpy(host).to(device)
+
+
+def der(frame_offsets, ref_offsets, ref_turns, prob_reco, hyp_offsets=None, hyp_turns=None, frame_item=None, item_offsets=None,
+        item_labels=None, uem_offsets=None, uem=None, collar=0, skip_overlap=False, n_ref_speakers=None, n_hyp_speakers=None,
+        want_matrix=False):
+    """nplda_der_i64: the counts of the diarization error rate and the optimal speaker mapping of P problems against Rn
+    recordings, in integer frames (include/nplda_hip.h has the definitions).  frame_offsets: Rn + 1 offsets of the
+    recordings' frames; ref_offsets: Rn + 1 offsets into ref_turns ((N, 3) begin, end, speaker); uem_offsets / uem ((U, 2)
+    begin, end) or neither: every frame of a recording; prob_reco: the recording of each problem, a sequence or what
+    der_problems() returns.  The hypotheses come in ONE of two forms: hyp_offsets (P + 1) into hyp_turns ((M, 3)), or
+    frame_item (one int32 per frame of every recording: the item that owns it, or -1) with item_offsets (P + 1) into
+    item_labels (a speaker or -1 per item of the problem).  Offsets: sequences or RaggedOffsets; tables: integer tensors (any
+    other integer array is copied to the device as int32).  collar in frames.  n_ref_speakers / n_hyp_speakers: speakers are
+    indices below these (default and most: nplda_der_max_speakers()); a turn or a label outside them counts as absent.
+    -> (counts (P, 6) int64 in the order of DER_COUNTS, map_ref (P, 64) int32, C (P, 64, 64) int32 or None), on the device."""
+    lib = _lib.load()
+    limit = int(lib.nplda_der_max_speakers())
+    tables = [t for t in (ref_turns, hyp_turns, frame_item, item_labels, uem) if isinstance(t, torch.Tensor) and t.is_cuda]
+    if isinstance(frame_offsets, RaggedOffsets):
+        dev = frame_offsets.dev.device
+    elif tables:
+        dev = tables[0].device
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if dev.type != "cuda":
+        raise ValueError("der runs on a HIP device")
+    collar = int(collar)
+    n_ref = limit if n_ref_speakers is None else int(n_ref_speakers)
+    n_hyp = limit if n_hyp_speakers is None else int(n_hyp_speakers)
+    if collar < 0 or not 0 <= n_ref <= limit or not 0 <= n_hyp <= limit:
+        raise ValueError(f"collar must not be negative and the speaker limits must lie in 0 .. {limit}")
+    fo = _der_offsets(frame_offsets, dev, "frame_offsets")
+    ro = _der_offsets(ref_offsets, dev, "ref_offsets", fo.P)
+    ref_turns = _der_table(ref_turns, ro.rows, 3, "ref_turns", dev)
+    if (uem_offsets is None) != (uem is None):
+        raise ValueError("give uem_offsets and uem, or neither")
+    uo = None
+    if uem_offsets is not None:
+        uo = _der_offsets(uem_offsets, dev, "uem_offsets", fo.P)
+        uem = _der_table(uem, uo.rows, 2, "uem", dev)
+    prepared = isinstance(prob_reco, tuple) and len(prob_reco) == 2 and isinstance(prob_reco[1], torch.Tensor)
+    host, pdev = prob_reco if prepared else der_problems(prob_reco, dev)
+    P = int(host.shape[0])
+    if pdev.device != dev or pdev.dtype != torch.int32 or tuple(pdev.shape) != (P,) or str(host.dtype) != "int32":
+        raise ValueError("prob_reco must be what der_problems() returns for this device")
+    if P and (int(host.min()) < 0 or int(host.max()) >= fo.P):
+        raise ValueError(f"prob_reco must name recordings 0 .. {fo.P - 1}")
+    by_turns = hyp_offsets is not None
+    if by_turns == (item_offsets is not None):
+        raise ValueError("give the hypotheses as hyp_offsets + hyp_turns or as frame_item + item_offsets + item_labels")
+    ho = io = None
+    if by_turns:
+        if frame_item is not None or item_labels is not None or hyp_turns is None:
+            raise ValueError("the turn form takes hyp_offsets and hyp_turns alone")
+        ho = _der_offsets(hyp_offsets, dev, "hyp_offsets", P)
+        hyp_turns = _der_table(hyp_turns, ho.rows, 3, "hyp_turns", dev)
+    else:
+        if hyp_turns is not None or frame_item is None or item_labels is None:
+            raise ValueError("the labelled-items form takes frame_item, item_offsets and item_labels alone")
+        io = _der_offsets(item_offsets, dev, "item_offsets", P)
+        frame_item = _der_table(frame_item, fo.rows, 0, "frame_item", dev)
+        item_labels = _der_table(item_labels, io.rows, 0, "item_labels", dev)
+    counts = torch.empty((P, len(DER_COUNTS)), dtype=torch.int64, device=dev)
+    map_ref = torch.empty((P, limit), dtype=torch.int32, device=dev)
+    C = torch.empty((P, limit, limit), dtype=torch.int32, device=dev) if want_matrix else None
+    if P == 0:
+        return counts, map_ref, C
+    wsb = lib.nplda_der_workspace_bytes(fo.hptr, fo.P)
+    if wsb == 0:
+        raise _lib.NpldaHipError("der: the frame offsets are outside what the kernel takes")
+    ws = torch.empty(wsb // 8, dtype=torch.int64, device=dev)
+
+    def nz(t):  # (an empty tensor has no address worth passing)
+        return _lib.ptr(t) if t is not None and t.numel() else None
+    with _lib.on_device(dev):
+        code = lib.nplda_der_i64(fo.hptr, _lib.ptr(fo.dev), fo.P, ro.hptr, _lib.ptr(ro.dev), nz(ref_turns),
+                                 uo.hptr if uo else None, _lib.ptr(uo.dev) if uo else None, nz(uem), collar,
+                                 1 if skip_overlap else 0, n_ref, n_hyp, host.ctypes.data, _lib.ptr(pdev), P,
+                                 ho.hptr if ho else None, _lib.ptr(ho.dev) if ho else None, nz(hyp_turns), nz(frame_item),
+                                 io.hptr if io else None, _lib.ptr(io.dev) if io else None, nz(item_labels),
+                                 _lib.ptr(counts), _lib.ptr(map_ref), _lib.ptr(C), _lib.ptr(ws), wsb, _lib.current_stream())
+    _lib.check(code, "nplda_der_i64")
+    return counts, map_ref, C
 
 
 def row_stats(S, topn=500, select="lowest"):

@@ -17,7 +17,9 @@ recording it does not list has no speech.  Without it the energy VAD of the pack
 --threshold, --calibration, --min-clusters, --linkage, --vb-plda, --vb-fa, --vb-fb, --vb-loop, --vb-max-iters: the
 clustering and the VB-HMM resegmentation, as in tools/cluster_xvectors.py (each recording on its own).
 The scp is worked through --recordings-per-call recordings at a time, so that the features and the workspaces stay
-bounded; speaker labels are counted on through the pieces.  Output: one RTTM line per speaker turn."""
+bounded; speaker labels are counted on through the pieces.  Output: one RTTM line per speaker turn.
+--ref-rttm: a reference RTTM; the overall diarization error rate of the output against it (collar 0.25 s, overlapped
+speech included) is printed after the RTTM is written (tools/score_rttm.py scores with other settings and per recording)."""
 import argparse
 import os
 import pickle
@@ -73,6 +75,7 @@ def main(argv=None):
     ap.add_argument("--vb-max-iters", type=int, default=40)
     ap.add_argument("--recordings-per-call", type=int, default=16)
     ap.add_argument("--rttm", required=True)
+    ap.add_argument("--ref-rttm", help="a reference RTTM: print the overall DER of the output (tools/score_rttm.py has the rest)")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -130,6 +133,9 @@ def main(argv=None):
     diarize.write_rttm(args.rttm, reco_ids, turns, args.frame_shift)
     print(f"{len(reco_ids)} recordings, {n_windows} windows -> {turns.shape[0]} turns of {base} speakers in {args.rttm}",
           file=sys.stderr)
+    if args.ref_rttm:
+        from neuralplda_amd import metrics
+        print(metrics.der(args.ref_rttm, args.rttm, frame_shift=args.frame_shift).lines()[-1])
 
 
 if __name__ == "__main__":
