@@ -504,7 +504,10 @@ int nplda_dplda_update_loss_f32(const float* paired, int64_t B, int64_t ld, int 
  *              minc_avg = sum(minc) / K.
  *   exact = 1: the true minimum of P_miss(th) + beta P_fa(th) over every distinct score and +inf ("target" iff
  *              s >= th), in fp64; eer (optional) = the equal error rate by linear interpolation at the crossing.
- * Labels: target iff t > 0.5, non-target iff t < 0.5 (as :407-408).  minc, thr (K), minc_avg (1), eer (1 or NULL)
+ * Labels: target iff t > 0.5, non-target iff t < 0.5 (as :407-408).  With exact = 0 the rates are divided by sum t and
+ * sum (1 - t) over ALL labels (as :411,413; exact for labels that are multiples of 2^-24), with exact = 1 by the class
+ * counts.  A trial whose score is NaN is in neither class (its label still enters the two sums).
+ * minc, thr (K), minc_avg (1), eer (1 or NULL)
  * are DEVICE floats.  N < 2^31.  The workspace size includes rocPRIM's temporary storage, whose size query needs a HIP
  * device: nplda_detcost_workspace_bytes returns 0 when there is none (or N is out of range). */
 size_t nplda_detcost_workspace_bytes(int64_t N);

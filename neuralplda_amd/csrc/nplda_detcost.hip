@@ -6,7 +6,7 @@
 // in which every sorted position is a candidate threshold: a binary search finds the start of its tie run, the two
 // prefix counts there give (#targets below, #non-targets at-or-above), the cost for every beta is formed and an
 // (value, index) arg-min is reduced wave -> block -> grid in a fixed order (ties -> lowest index, the first
-// occurrence a CPU torch.min returns).  HBM-bound: ~N * (sort passes + 24 B) bytes; 2^20 scores in ~100 us.
+// occurrence a CPU torch.min returns).  HBM-bound: ~N * (sort passes + 32 B) bytes; 2^20 scores in ~100 us.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -30,19 +30,71 @@ __device__ __forceinline__ Best better(Best a, Best b) {
 }
 
 // label code: 1 target (t > 0.5), 0 non-target (t < 0.5), excluded otherwise (utils/models.py:407-408);
-// packed as (target << 32) | non-target so that ONE 64-bit prefix sum carries both counts
-__global__ __launch_bounds__(256) void label_kernel(const float* __restrict__ t, long long n,
-                                                    unsigned long long* __restrict__ lab) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float v = t[i];
-    lab[i] = v > 0.5f ? (1ull << 32) : (v < 0.5f ? 1ull : 0ull);
+// packed as (target << 32) | non-target so that ONE 64-bit prefix sum carries both counts.
+// A trial whose score is NaN is excluded whatever its label, and its sort key becomes the canonical positive NaN, which
+// the radix sort puts behind +inf: the NaNs form the tail of the sorted array, where `<` and `==` stay monotone (a
+// NaN with the sign bit set would sort in front of -inf and break every binary search).
+// The same pass forms the reference's normalisers sum(t) and sum(1 - t) over ALL labels (utils/models.py:411,413) in
+// 2^-24 fixed point, one pair of partial sums per block: integer adds commute, so the totals do not depend on any
+// order, and they are exact for labels that are multiples of 2^-24 (every float32 in [0.5, 1]; 0/1 labels give the
+// class counts).  The sweep kernel adds the partials up; no atomics, nothing to zero.
+constexpr int kLabelBlocks = 1024;
+constexpr double kLabelScale = 16777216.0;  // 2^24
+constexpr float kLabelClamp = 256.0f;       // |label| beyond this saturates: 2^31 trials * 256 * 2^24 < 2^63
+
+__device__ __forceinline__ long long label_fixed(float v) {
+    v = v != v ? 0.0f : fminf(fmaxf(v, -kLabelClamp), kLabelClamp);  // a NaN label adds nothing
+    return __double2ll_rn((double)v * kLabelScale);
+}
+
+// block sum of a pair of 64-bit integers, returned in every thread
+__device__ __forceinline__ void block_sum2(long long& q1, long long& q0, long long (*red)[2]) {
+    for (int off = 32; off > 0; off >>= 1) {
+        q1 += __shfl_xor(q1, off);
+        q0 += __shfl_xor(q0, off);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { red[wave][0] = q1; red[wave][1] = q0; }
+    __syncthreads();
+    q1 = red[0][0] + red[1][0] + red[2][0] + red[3][0];
+    q0 = red[0][1] + red[1][1] + red[2][1] + red[3][1];
+}
+
+__global__ __launch_bounds__(256) void label_kernel(const float* __restrict__ s, const float* __restrict__ t, long long n,
+                                                    float* __restrict__ key, unsigned long long* __restrict__ lab,
+                                                    long long* __restrict__ lpart) {  // [gridDim.x][2]
+    __shared__ long long red[4][2];
+    long long q1 = 0, q0 = 0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const float v = t[i], x = s[i];
+        const bool nan = x != x;
+        key[i] = nan ? __uint_as_float(0x7fc00000u) : x;
+        lab[i] = nan ? 0ull : (v > 0.5f ? (1ull << 32) : (v < 0.5f ? 1ull : 0ull));
+        q1 += label_fixed(v);
+        q0 += label_fixed(__fsub_rn(1.0f, v));
+    }
+    block_sum2(q1, q0, red);
+    if (threadIdx.x == 0) {
+        lpart[2 * blockIdx.x] = q1;
+        lpart[2 * blockIdx.x + 1] = q0;
+    }
+}
+
+// pm + beta * pf with two roundings, as the reference's float32 tensors compute it.  __fmul_rn / __fadd_rn are plain * and +
+// in HIP's headers, which the compiler's default contraction turns into one fma (a last-bit difference from the reference,
+// e.g. 1/86 + 99 * (170/171)); the operators below carry no permission to contract.
+__device__ __forceinline__ float cost_unfused(float pm, float beta, float pf) {
+#pragma clang fp contract(off)
+    const float m = beta * pf;
+    return pm + m;
 }
 
 struct SweepArgs {
     const float* key;                  // sorted scores
     const unsigned long long* lab;     // sorted packed labels
     const unsigned long long* pref;    // exclusive prefix sums of lab
+    const long long* lpart;            // [nlabel][2] partial sums of t and 1 - t over all labels, 2^-24 fixed point
+    int nlabel;
     long long n;
     int K, exact;
     float beta[kMaxBeta];
@@ -67,7 +119,25 @@ __global__ __launch_bounds__(256) void sweep_kernel(const SweepArgs a) {
     Best best[kMaxBeta + 1];
 #pragma unroll
     for (int k = 0; k <= kMaxBeta; ++k) best[k] = Best{INFINITY, 0x7fffffffffffffffll};
-    const float fnt = (float)Nt, fnn = (float)Nn;
+    // reference mode divides by the label SUMS (one rounding to float32), exact mode by the class counts
+    float fnt = 0.f, fnn = 0.f;
+    if (!a.exact) {
+        __shared__ long long lred[4][2];
+        __shared__ float fsum[2];
+        long long q1 = 0, q0 = 0;
+        for (int j = threadIdx.x; j < a.nlabel; j += 256) {
+            q1 += a.lpart[2 * j];
+            q0 += a.lpart[2 * j + 1];
+        }
+        block_sum2(q1, q0, lred);
+        if (threadIdx.x == 0) {
+            fsum[0] = (float)((double)q1 * (1.0 / kLabelScale));
+            fsum[1] = (float)((double)q0 * (1.0 / kLabelScale));
+        }
+        __syncthreads();
+        fnt = fsum[0];
+        fnn = fsum[1];
+    }
     for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < n; p += (long long)gridDim.x * 256) {
         const float v = a.key[p];
         if (!a.exact) {
@@ -83,9 +153,10 @@ __global__ __launch_bounds__(256) void sweep_kernel(const SweepArgs a) {
             const long long rank = (long long)(a.pref[p] >> 32);  // index in the sorted target list
 #pragma unroll
             for (int k = 0; k < kMaxBeta; ++k)
-                if (k < a.K) best[k] = better(best[k], Best{(double)__fadd_rn(pm, __fmul_rn(a.beta[k], pf)), rank});
+                if (k < a.K) best[k] = better(best[k], Best{(double)cost_unfused(pm, a.beta[k], pf), rank});
         } else {
             // every distinct score is a threshold ("target" iff s >= th); +inf is added by the final kernel
+            if (v != v) continue;                      // NaN scores (the tail) are no thresholds
             if (p > 0 && a.key[p - 1] == v) continue;  // not the start of its tie run
             const unsigned long long pr = a.pref[p];
             const double pm = (double)(long long)(pr >> 32) / (double)(Nt > 0 ? Nt : 1);
@@ -216,7 +287,7 @@ __global__ __launch_bounds__(64 * (kMaxBeta + 1)) void final_kernel(const FinalA
 }
 
 struct Plan {
-    size_t o_keys, o_lab_in, o_lab, o_pref, o_part, o_tmp, tmp_bytes, total;
+    size_t o_keys_in, o_keys, o_lab_in, o_lab, o_pref, o_part, o_lpart, o_tmp, tmp_bytes, total;
 };
 
 int make_plan(long long n, Plan* p) {
@@ -232,11 +303,13 @@ int make_plan(long long n, Plan* p) {
         return (int)e;
     auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     size_t o = 0;
+    p->o_keys_in = o; o += up(nn * sizeof(float));
     p->o_keys = o; o += up(nn * sizeof(float));
     p->o_lab_in = o; o += up(nn * sizeof(unsigned long long));
     p->o_lab = o; o += up(nn * sizeof(unsigned long long));
     p->o_pref = o; o += up(nn * sizeof(unsigned long long));
     p->o_part = o; o += up((size_t)kSweepBlocks * (kMaxBeta + 1) * sizeof(Best));
+    p->o_lpart = o; o += up((size_t)kLabelBlocks * 2 * sizeof(long long));
     p->tmp_bytes = sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
     p->o_tmp = o; o += up(p->tmp_bytes);
     p->total = o;
@@ -266,17 +339,21 @@ int nplda_detcost_sweep_f32(const float* scores, const float* target, int64_t N,
     if (workspace_bytes < p.total) return NPLDA_ENOSPC;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
+    float* keys_in = (float*)(ws + p.o_keys_in);
     float* keys = (float*)(ws + p.o_keys);
+    long long* lpart = (long long*)(ws + p.o_lpart);
     unsigned long long* lab_in = (unsigned long long*)(ws + p.o_lab_in);
     unsigned long long* lab = (unsigned long long*)(ws + p.o_lab);
     unsigned long long* pref = (unsigned long long*)(ws + p.o_pref);
     Best* part = (Best*)(ws + p.o_part);
     int nblocks = 0;
     if (N > 0) {
-        hipLaunchKernelGGL(label_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, target, (long long)N, lab_in);
+        const int nlabel = (int)((N + 255) / 256 < kLabelBlocks ? (N + 255) / 256 : kLabelBlocks);
+        hipLaunchKernelGGL(label_kernel, dim3(nlabel), dim3(256), 0, st, scores, target, (long long)N, keys_in, lab_in, lpart);
         if (int rc = nplda_launch_status()) return rc;
         size_t tb = p.tmp_bytes;
-        if (hipError_t e = rocprim::radix_sort_pairs(ws + p.o_tmp, tb, scores, keys, (const unsigned long long*)lab_in,
+        if (hipError_t e = rocprim::radix_sort_pairs(ws + p.o_tmp, tb, (const float*)keys_in, keys,
+                                                     (const unsigned long long*)lab_in,
                                                      lab, (size_t)N, 0, 32, st))
             return (int)e;
         tb = p.tmp_bytes;
@@ -285,7 +362,7 @@ int nplda_detcost_sweep_f32(const float* scores, const float* target, int64_t N,
             return (int)e;
         nblocks = (int)((N + 255) / 256 < kSweepBlocks ? (N + 255) / 256 : kSweepBlocks);
         SweepArgs a;
-        a.key = keys; a.lab = lab; a.pref = pref; a.n = N; a.K = K; a.exact = exact ? 1 : 0; a.part = part;
+        a.key = keys; a.lab = lab; a.pref = pref; a.lpart = lpart; a.nlabel = nlabel; a.n = N; a.K = K; a.exact = exact ? 1 : 0; a.part = part;
         for (int k = 0; k < kMaxBeta; ++k) a.beta[k] = k < K ? betas[k] : 0.f;
         hipLaunchKernelGGL(sweep_kernel, dim3(nblocks), dim3(256), 0, st, a);
         if (int rc = nplda_launch_status()) return rc;

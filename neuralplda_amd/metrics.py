@@ -6,8 +6,14 @@ CPU tensors are moved to the HIP device first — like the rest of the package t
 
 * reference_semantics=True (default): bit-compatible with the reference INCLUDING its quirks
   (utils/models.py:23-27 `arr2val`): the "count" is the last index of torch.where (= count - 1) and
-  1.0 when the set is empty; thresholds are swept over the target scores only.
-* reference_semantics=False: the exact minimum of P_miss + beta * P_fa over all thresholds.
+  1.0 when the set is empty; thresholds are swept over the target scores only; the classes are target > 0.5 and
+  target < 0.5, but the two rates are divided by target.sum() and (1 - target).sum() over ALL labels, so a label
+  outside {0, 1} is in neither class and still in both normalisers.
+* reference_semantics=False: the exact minimum of P_miss + beta * P_fa over all thresholds, the rates divided by the
+  class counts.
+
+Trials whose score is NaN are ignored by minc, minc_exact and eer: they are in neither class and change no other
+trial's counts (in reference mode their labels still enter the two sums, which the reference forms over all labels).
 
 Calibration-sensitive metrics (no reference counterpart; kernel nplda_calib_costs_*, csrc/nplda_calib.hip) take
 log-likelihood ratios instead of arbitrary scores:
@@ -69,18 +75,19 @@ def _sweep(output, target, betas, exact, want_eer=False):
 
 
 def minc(output, target, betas, reference_semantics=True):
-    """Returns (minc_avg: 0-d float32 tensor, {beta: 0-d threshold tensor})."""
+    """Returns (minc_avg: 0-d float32 tensor, {beta: 0-d threshold tensor}).  Trials whose score is NaN are ignored."""
     _, th, avg, _ = _sweep(output, target, list(betas), exact=not reference_semantics)
     return avg.reshape(()), {beta: th[k] for k, beta in enumerate(betas)}
 
 
 def minc_exact(output, target, betas):
-    """True minimum detection cost: decide 'target' iff s >= th, th swept over every score and +inf."""
+    """True minimum detection cost: decide 'target' iff s >= th, th swept over every score and +inf.  Trials whose score
+    is NaN are ignored."""
     return minc(output, target, betas, reference_semantics=False)
 
 
 def eer(output, target):
-    """Equal error rate (linear interpolation at the P_miss / P_fa crossing)."""
+    """Equal error rate (linear interpolation at the P_miss / P_fa crossing).  Trials whose score is NaN are ignored."""
     _, _, _, e = _sweep(output, target, [1.0], exact=True, want_eer=True)
     return float(e.item())
 

@@ -103,6 +103,21 @@ def save(name, **arrays):
     print(f"{name}: {os.path.getsize(path) / 1024:.0f} KB")
 
 
+def g5b():
+    """G5b: NeuralPlda.minc on labels outside {0, 1}.  The reference picks the classes with t > 0.5 / t < 0.5 but divides by
+    target.sum() and (1 - target).sum() over all labels; quantised scores make ties.  Own RNG stream: no other fixture moves."""
+    rg = np.random.default_rng(55)
+    N = 256
+    tb = np.asarray([0.0, 0.25, 0.5, 0.75, 1.0], np.float32)[rg.integers(0, 5, N)]
+    sb = (np.round((rg.standard_normal(N) * 0.5 + 0.5 * (tb > 0.5)) * 16) / 16).astype(np.float32)
+    betas = (1.0, 9.9)
+    m = refm.NeuralPlda(NC(D0=64, D1=24, D2=20, beta=betas))
+    with torch.no_grad():
+        minc, th = m.minc(torch.from_numpy(sb), torch.from_numpy(tb))
+    save("g5b_metrics_labels.npz", s=sb, t=tb, beta=np.asarray(betas), minc=np.asarray(minc),
+         minc_th=np.asarray([th[b].item() for b in betas]))
+
+
 def main():
     mean_vec = kf.read_vector(f"{REF}/Kaldi_Models/mean.vec")
 
@@ -259,6 +274,8 @@ def main():
          cdet=c5, softcdet=sc5, xent=xe5, minc=np.asarray(minc5), minc_th=np.asarray([th5[99.0].item(), th5[199.0].item()]),
          th_after_update=th_after, s_sep=ssep, minc_sep=np.asarray(mincsep),
          minc_sep_th=np.asarray([thsep[99.0].item(), thsep[199.0].item()]))
+
+    g5b()
 
     # ---- G6: AS-norm script ------------------------------------------------------------------------
     enr = [f"enr{i}" for i in range(5)]
@@ -451,4 +468,7 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["g5b"]:  # one fixture alone
+        g5b()
+    else:
+        main()
