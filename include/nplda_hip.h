@@ -508,8 +508,9 @@ int nplda_dplda_update_loss_f32(const float* paired, int64_t B, int64_t ld, int 
  * sum (1 - t) over ALL labels (as :411,413; exact for labels that are multiples of 2^-24), with exact = 1 by the class
  * counts.  A trial whose score is NaN is in neither class (its label still enters the two sums).
  * minc, thr (K), minc_avg (1), eer (1 or NULL)
- * are DEVICE floats.  N < 2^31.  The workspace size includes rocPRIM's temporary storage, whose size query needs a HIP
- * device: nplda_detcost_workspace_bytes returns 0 when there is none (or N is out of range). */
+ * are DEVICE floats.  N < 2^31.  The workspace size needs no device: for the sort and the scan it reserves
+ * max(N, 1) * 14 bytes + 4 MiB from N alone, and the call returns NPLDA_ENOSPC if the sort library asks for more.
+ * nplda_detcost_workspace_bytes returns 0 when N is out of range. */
 size_t nplda_detcost_workspace_bytes(int64_t N);
 int nplda_detcost_sweep_f32(const float* scores, const float* target, int64_t N, const float* betas, int K, int exact,
                             float* minc, float* thr, float* minc_avg, float* eer, void* workspace,

@@ -28,8 +28,6 @@ constexpr int kNone = 0x7fffffff;   // "no partner"
 constexpr int kBlockScanRows = 8;   // a merge of a problem above kSmallN rows with up to this many rows to scan again has
 constexpr int kSmallN = 2048;       // the whole block scan each; any other merge gives every such row to one wave
 
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // ---- host: the ragged layout ------------------------------------------------------------------------------------------------
 
 struct RaggedPlan {

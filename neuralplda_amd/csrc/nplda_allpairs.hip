@@ -33,8 +33,6 @@ struct WsLayout {
     int nblk, ncnt;
 };
 
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 WsLayout ws_layout(int64_t N, int Dp) {
     WsLayout L;
     L.Np = (N + kRowTile - 1) / kRowTile * kRowTile;

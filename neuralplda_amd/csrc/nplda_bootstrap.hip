@@ -2,8 +2,8 @@
 // trial sides, every replicate an integer re-weighting of ONE sorted trial list — N x B weighted updates, not B sorts.
 // Stages, all enqueued on one stream with no read-back (the launch count depends on N, B, G1, G2 only):
 //   prep     scores -> sort keys (a NaN score gets the key -inf and is dead), the identity permutation
-//   sort     rocprim::radix_sort_pairs of (key, index)                                             [as nplda_detcost.hip]
-//   gather   label code, tie-run start flag, g1, g2 and (is_llr) the Cllr term of every trial, in sorted order
+//   sort     radix sort of the (key, index) pairs                                                   [trials::sort_pairs]
+//   gather   label code (the classes of nplda_trials.h), tie-run start flag, g1, g2 and (is_llr) the Cllr term of every trial, in sorted order
 // then per tile of kTile = 64 replicates (row 0, the point estimate, is replicate 0 of tile 0 with all counts 1):
 //   draw     the multinomial draw counts of both sides by integer atomics into a [group][replicate in tile] table
 //   pack     the counts as saturating bytes: one trial's look-up is 64 consecutive bytes across a wave
@@ -21,9 +21,7 @@
 
 #include <cmath>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include "nplda_common.h"
+#include "nplda_trials.h"
 
 namespace {
 
@@ -40,6 +38,8 @@ constexpr unsigned long long kGold = 0x9e3779b97f4a7c15ull;
 
 enum { OP_SUM = 0, OP_SCAN = 1, OP_MAX = 2, OP_MIN = 3 };
 enum { CODE_NON = 0, CODE_TGT = 1, CODE_IGNORED = 2, CODE_DEAD = 3, FLAG_START = 4 };
+static_assert((int)CODE_NON == (int)trials::kNonTarget && (int)CODE_TGT == (int)trials::kTarget,
+              "a class code is trials::label_class's value");
 
 __host__ __device__ inline unsigned long long mix(unsigned long long x) {  // the splitmix64 finaliser
     x ^= x >> 30;
@@ -80,7 +80,8 @@ __global__ __launch_bounds__(256) void gather_kernel(const GatherArgs a) {
     if (p >= a.n) return;
     const unsigned i = a.idx[p];
     const float s = a.scores[i], t = a.target[i];
-    int code = s != s ? CODE_DEAD : (t > 0.5f ? CODE_TGT : (t < 0.5f ? CODE_NON : CODE_IGNORED));
+    const int cls = trials::label_class(t);
+    int code = s != s ? CODE_DEAD : (cls == trials::kNeither ? CODE_IGNORED : cls);
     int ga = a.g1[i], gb = a.g2 ? a.g2[i] : 0;
     if (ga < 0 || ga >= a.G1 || (a.g2 && (gb < 0 || gb >= a.G2))) {  // never used as a table index
         code = CODE_DEAD;
@@ -321,16 +322,6 @@ __global__ __launch_bounds__(64 * kRedWaves) void reduce_kernel(const ReduceArgs
     }
 }
 
-__device__ __forceinline__ long long lower_bound(const float* __restrict__ key, long long n, float v) {
-    long long lo = 0, hi = n;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (key[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 struct FinishArgs {
     WalkArgs w;
     int tile, B, llr, g2;
@@ -362,7 +353,7 @@ __global__ __launch_bounds__(64) void finish_kernel(const FinishArgs f) {
         const long long c = (long long)cross, rc = c / kRun;
         const double ctg = a.part[(size_t)(Q1 + K + 1) * qs + rc * kTile + l];
         const double cfa = a.part[(size_t)(Q1 + K + 2) * qs + rc * kTile + l];
-        const long long q = lower_bound(a.key, a.n, a.key[c - 1]), rq = q / kRun;
+        const long long q = trials::lower_bound(a.key, a.n, a.key[c - 1]), rq = q / kRun;
         double t0 = 0.0, n0 = 0.0;
         for (long long p = rq * kRun + lane; p < q; p += 64) {
             const int code = a.fl[p] & 3;
@@ -407,29 +398,27 @@ struct Plan {
     int nruns, nchunks;
 };
 
-// rocPRIM's own size query needs a device; the plan must not, so the sort's temporary storage is reserved from N (its
-// alternate key and value buffers and digit counters) and the entry point checks the actual request against it
+// the sort's temporary storage is reserved from N, without a device (trials::sort_reserve_bytes)
 void make_plan(long long n, long long G1, long long G2, Plan* p) {
     const size_t nn = (size_t)n, gg = (size_t)(G1 + G2);
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     p->nruns = (int)((n + kRun - 1) / kRun);
     p->nchunks = (p->nruns + kChunkRuns - 1) / kChunkRuns;
     size_t o = 0;
     p->o_flags = o; o += 256;
-    p->o_key_in = o; o += up(nn * 4);
-    p->o_key = o; o += up(nn * 4);
-    p->o_idx_in = o; o += up(nn * 4);
-    p->o_idx = o; o += up(nn * 4);
-    p->o_fl = o; o += up(nn);
-    p->o_g1s = o; o += up(nn * 4);
-    p->o_g2s = o; o += up(nn * 4);
-    p->o_sp = o; o += up(nn * 8);
-    p->o_tab32 = o; o += up(gg * kTile * 4);
-    p->o_tab8 = o; o += up(gg * kTile);
-    p->o_part = o; o += up((size_t)kMaxQ * p->nruns * kTile * 8);
-    p->o_ctot = o; o += up((size_t)kMaxQ * p->nchunks * kTile * 8);
-    p->o_tot = o; o += up((size_t)kMaxQ * kTile * 8);
-    p->tmp_bytes = up(nn * 8 + 2 * nn + ((size_t)4 << 20));
+    p->o_key_in = o; o += up256(nn * 4);
+    p->o_key = o; o += up256(nn * 4);
+    p->o_idx_in = o; o += up256(nn * 4);
+    p->o_idx = o; o += up256(nn * 4);
+    p->o_fl = o; o += up256(nn);
+    p->o_g1s = o; o += up256(nn * 4);
+    p->o_g2s = o; o += up256(nn * 4);
+    p->o_sp = o; o += up256(nn * 8);
+    p->o_tab32 = o; o += up256(gg * kTile * 4);
+    p->o_tab8 = o; o += up256(gg * kTile);
+    p->o_part = o; o += up256((size_t)kMaxQ * p->nruns * kTile * 8);
+    p->o_ctot = o; o += up256((size_t)kMaxQ * p->nchunks * kTile * 8);
+    p->o_tot = o; o += up256((size_t)kMaxQ * kTile * 8);
+    p->tmp_bytes = trials::sort_reserve_bytes(nn, 4, 4);
     p->o_tmp = o; o += p->tmp_bytes;
     p->total = o;
 }
@@ -487,20 +476,12 @@ int nplda_bootstrap_f32(const float* scores, const float* target, const int32_t*
     unsigned* idx = (unsigned*)(ws + p.o_idx);
     unsigned* tab32 = (unsigned*)(ws + p.o_tab32);
     unsigned char* tab8 = (unsigned char*)(ws + p.o_tab8);
-    size_t sort_bytes = 0;
-    if (hipError_t e = rocprim::radix_sort_pairs(nullptr, sort_bytes, (const float*)nullptr, (float*)nullptr,
-                                                 (const unsigned*)nullptr, (unsigned*)nullptr, (size_t)N, 0, 32, st))
-        return (int)e;
-    if (sort_bytes > p.tmp_bytes) return NPLDA_ENOSPC;
     const bool llr = is_llr != 0, has2 = G2 > 0;
     const unsigned nblk = (unsigned)((N + 255) / 256);
     if (hipError_t e = hipMemsetAsync(flags, 0, 256, st)) return (int)e;
     hipLaunchKernelGGL(prep_kernel, dim3(nblk), dim3(256), 0, st, scores, (long long)N, key_in, idx_in);
     if (int rc = nplda_launch_status()) return rc;
-    size_t tb = p.tmp_bytes;
-    if (hipError_t e = rocprim::radix_sort_pairs(ws + p.o_tmp, tb, (const float*)key_in, key, (const unsigned*)idx_in, idx,
-                                                 (size_t)N, 0, 32, st))
-        return (int)e;
+    if (int rc = trials::sort_pairs(ws + p.o_tmp, p.tmp_bytes, key_in, key, idx_in, idx, (size_t)N, st)) return rc;
     GatherArgs g;
     g.scores = scores; g.target = target; g.g1 = g1; g.g2 = g2; g.key = key; g.idx = idx; g.n = N;
     g.G1 = (int)G1; g.G2 = (int)G2; g.llr = llr;

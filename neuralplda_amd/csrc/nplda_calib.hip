@@ -14,7 +14,7 @@
 
 #include <cmath>
 
-#include "nplda_common.h"
+#include "nplda_trials.h"
 
 namespace {
 
@@ -81,13 +81,11 @@ __device__ __forceinline__ void reduce_partials(const double* __restrict__ part,
     __syncthreads();
 }
 
-__device__ __forceinline__ int label_of(float t) { return t > 0.5f ? 1 : (t < 0.5f ? 0 : -1); }  // as nplda_detcost
-
 __global__ __launch_bounds__(kBlock) void count_kernel(const float* __restrict__ t, long long n, State* st) {
     if (st->done) return;
     unsigned ct = 0, cn = 0;
     for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
-        const int l = label_of(t[i]);
+        const int l = trials::label_class(t[i]);  // 1 target, 0 non-target, -1 neither
         ct += l == 1;
         cn += l == 0;
     }
@@ -120,7 +118,7 @@ __global__ __launch_bounds__(kBlock) void pass_kernel(const T* __restrict__ X, l
     for (int k = 0; k <= K; ++k) a[k] = theta[k];
     const double wt = p_target / (double)st->nt, wn = (1.0 - p_target) / (double)st->nn;
     for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
-        const int l = label_of(t[i]);
+        const int l = trials::label_class(t[i]);
         if (l < 0) continue;  // neither class: weight 0, the row is not read
         double x[K + 1];
 #pragma unroll
@@ -326,7 +324,7 @@ __global__ __launch_bounds__(kBlock) void gauss_sum_kernel(const T* __restrict__
                                                            long long n, double* __restrict__ part) {
     double acc[4] = {0.0, 0.0, 0.0, 0.0};  // n_tgt, sum_tgt, n_non, sum_non
     for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
-        const int l = label_of(t[i]);
+        const int l = trials::label_class(t[i]);
         if (l < 0) continue;
         const double v = (double)s[i];
         acc[0] += l ? 1.0 : 0.0;  // adding 0.0 is exact: both classes in straight-line code
@@ -355,7 +353,7 @@ __global__ __launch_bounds__(kBlock) void gauss_dev_kernel(const T* __restrict__
     const double mt = st->cur[1], mn = st->cur[3];
     double acc[4] = {0.0, 0.0, 0.0, 0.0};  // sum d_tgt, sum d_tgt^2, sum d_non, sum d_non^2
     for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
-        const int l = label_of(t[i]);
+        const int l = trials::label_class(t[i]);
         if (l < 0) continue;
         const double v = (double)s[i];
         const double d = v - (l ? mt : mn);
@@ -419,7 +417,7 @@ __global__ __launch_bounds__(kBlock) void costs_kernel(const T* __restrict__ llr
 #pragma unroll
     for (int q = 0; q < kCostQ; ++q) acc[q] = 0.0;
     for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
-        const int l = label_of(t[i]);
+        const int l = trials::label_class(t[i]);
         if (l < 0) continue;
         const double v = (double)llr[i];
         const double sp = log1p(exp(-fabs(v))) + fmax(l ? -v : v, 0.0);

@@ -71,6 +71,9 @@ static inline int nplda_launch_status() {
 
 static inline bool nplda_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
+// workspace regions start on 256-byte boundaries
+static inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
 // An MFMA accumulator fragment of a (16 features x 16 rows) block has lane 16 g + j on row j, features 4 g .. 4 g + 3: stored
 // as it is, CONSECUTIVE lanes write 16 bytes to sixteen different rows, and a CU gets 15 B / clk out of such stores where
 // pieces of 64 contiguous bytes per four lanes get 29 - 43 (tools/exp_store_patterns.hip, round 6).  This moves the rows to

@@ -27,8 +27,6 @@ constexpr long long kDerMaxFrames = 1ll << 40;     // frames per call
 constexpr unsigned kInUem = 1u, kInCollar = 2u;    // flag bits; a frame is scored when its flag == kInUem
 constexpr int kNCounts = 6;                        // scored, total, miss, fa, sum of min(|R|, |H|), matched
 
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // ---- host: the checks every entry point shares ----------------------------------------------------------------------------------
 
 // P + 1 non-decreasing offsets that start at 0 -> the last one, or -1

@@ -7,14 +7,12 @@
 // prefix counts there give (#targets below, #non-targets at-or-above), the cost for every beta is formed and an
 // (value, index) arg-min is reduced wave -> block -> grid in a fixed order (ties -> lowest index, the first
 // occurrence a CPU torch.min returns).  HBM-bound: ~N * (sort passes + 32 B) bytes; 2^20 scores in ~100 us.
+// The trial rule, the sort keys and the sort front end are nplda_trials.h.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
-#include "nplda_common.h"
+#include "nplda_trials.h"
 
 namespace {
 
@@ -29,11 +27,8 @@ __device__ __forceinline__ Best better(Best a, Best b) {
     return (b.v < a.v || (b.v == a.v && b.i < a.i)) ? b : a;
 }
 
-// label code: 1 target (t > 0.5), 0 non-target (t < 0.5), excluded otherwise (utils/models.py:407-408);
-// packed as (target << 32) | non-target so that ONE 64-bit prefix sum carries both counts.
-// A trial whose score is NaN is excluded whatever its label, and its sort key becomes the canonical positive NaN, which
-// the radix sort puts behind +inf: the NaNs form the tail of the sorted array, where `<` and `==` stay monotone (a
-// NaN with the sign bit set would sort in front of -inf and break every binary search).
+// Sort key and packed class count of every trial (trials::key_and_count): a trial that its label excludes keeps its
+// score as the key — exact mode takes every distinct score as a threshold — and only a NaN score moves to the tail.
 // The same pass forms the reference's normalisers sum(t) and sum(1 - t) over ALL labels (utils/models.py:411,413) in
 // 2^-24 fixed point, one pair of partial sums per block: integer adds commute, so the totals do not depend on any
 // order, and they are exact for labels that are multiples of 2^-24 (every float32 in [0.5, 1]; 0/1 labels give the
@@ -66,10 +61,8 @@ __global__ __launch_bounds__(256) void label_kernel(const float* __restrict__ s,
     __shared__ long long red[4][2];
     long long q1 = 0, q0 = 0;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const float v = t[i], x = s[i];
-        const bool nan = x != x;
-        key[i] = nan ? __uint_as_float(0x7fc00000u) : x;
-        lab[i] = nan ? 0ull : (v > 0.5f ? (1ull << 32) : (v < 0.5f ? 1ull : 0ull));
+        const float v = t[i];
+        trials::key_and_count<trials::Excluded::kKeepScore>(s[i], v, key[i], lab[i]);
         q1 += label_fixed(v);
         q0 += label_fixed(__fsub_rn(1.0f, v));
     }
@@ -100,16 +93,6 @@ struct SweepArgs {
     float beta[kMaxBeta];
     Best* part;                        // [kSweepBlocks][K + 1]  (slot K: first threshold with P_miss >= P_fa)
 };
-
-__device__ __forceinline__ long long lower_bound(const float* __restrict__ key, long long n, float v) {
-    long long lo = 0, hi = n;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (key[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(256) void sweep_kernel(const SweepArgs a) {
     __shared__ Best red[4][kMaxBeta + 1];
@@ -144,7 +127,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(const SweepArgs a) {
             // thresholds = target scores only; counts with the arr2val quirk: "count" = last index of torch.where
             // (count - 1), 1.0 when the set is empty; float32 arithmetic in the reference's order (no fma)
             if (!(a.lab[p] >> 32)) continue;
-            const long long lb = lower_bound(a.key, n, v);
+            const long long lb = trials::lower_bound(a.key, n, v);
             const unsigned long long pr = a.pref[lb];
             const long long c_lt = (long long)(pr >> 32);
             const long long c_ge = Nn - (long long)(pr & 0xffffffffull);
@@ -273,7 +256,7 @@ __global__ __launch_bounds__(64 * (kMaxBeta + 1)) void final_kernel(const FinalA
                 if (c.i == 0) {
                     e = (float)((pm1 + pf1) / 2);
                 } else {
-                    const long long q = lower_bound(a.key, n, a.key[c.i - 1]);  // previous distinct threshold
+                    const long long q = trials::lower_bound(a.key, n, a.key[c.i - 1]);  // previous distinct threshold
                     double pm0, pf0;
                     rates(q, pm0, pf0);
                     const double x0 = pm0 - pf0, x1 = pm1 - pf1;
@@ -290,30 +273,19 @@ struct Plan {
     size_t o_keys_in, o_keys, o_lab_in, o_lab, o_pref, o_part, o_lpart, o_tmp, tmp_bytes, total;
 };
 
-int make_plan(long long n, Plan* p) {
+void make_plan(long long n, Plan* p) {
     const size_t nn = (size_t)(n > 0 ? n : 1);
-    size_t sort_bytes = 0, scan_bytes = 0;
-    if (hipError_t e = rocprim::radix_sort_pairs(nullptr, sort_bytes, (const float*)nullptr, (float*)nullptr,
-                                                 (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                                 nn, 0, 32, (hipStream_t)0))
-        return (int)e;
-    if (hipError_t e = rocprim::exclusive_scan(nullptr, scan_bytes, (const unsigned long long*)nullptr,
-                                               (unsigned long long*)nullptr, 0ull, nn,
-                                               rocprim::plus<unsigned long long>(), (hipStream_t)0))
-        return (int)e;
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     size_t o = 0;
-    p->o_keys_in = o; o += up(nn * sizeof(float));
-    p->o_keys = o; o += up(nn * sizeof(float));
-    p->o_lab_in = o; o += up(nn * sizeof(unsigned long long));
-    p->o_lab = o; o += up(nn * sizeof(unsigned long long));
-    p->o_pref = o; o += up(nn * sizeof(unsigned long long));
-    p->o_part = o; o += up((size_t)kSweepBlocks * (kMaxBeta + 1) * sizeof(Best));
-    p->o_lpart = o; o += up((size_t)kLabelBlocks * 2 * sizeof(long long));
-    p->tmp_bytes = sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
-    p->o_tmp = o; o += up(p->tmp_bytes);
+    p->o_keys_in = o; o += up256(nn * sizeof(float));
+    p->o_keys = o; o += up256(nn * sizeof(float));
+    p->o_lab_in = o; o += up256(nn * sizeof(unsigned long long));
+    p->o_lab = o; o += up256(nn * sizeof(unsigned long long));
+    p->o_pref = o; o += up256(nn * sizeof(unsigned long long));
+    p->o_part = o; o += up256((size_t)kSweepBlocks * (kMaxBeta + 1) * sizeof(Best));
+    p->o_lpart = o; o += up256((size_t)kLabelBlocks * 2 * sizeof(long long));
+    p->tmp_bytes = trials::sort_reserve_bytes(nn, sizeof(float), sizeof(unsigned long long));
+    p->o_tmp = o; o += p->tmp_bytes;
     p->total = o;
-    return 0;
 }
 
 }  // namespace
@@ -323,7 +295,7 @@ extern "C" {
 size_t nplda_detcost_workspace_bytes(int64_t N) {
     if (N < 0 || N > 0x7fffffffll) return 0;
     Plan p;
-    if (make_plan(N, &p)) return 0;
+    make_plan(N, &p);
     return p.total;
 }
 
@@ -335,7 +307,7 @@ int nplda_detcost_sweep_f32(const float* scores, const float* target, int64_t N,
     if (N > 0 && (!scores || !target)) return NPLDA_EINVAL;
     if (!workspace || !nplda_aligned16(workspace)) return NPLDA_EINVAL;
     Plan p;
-    if (int rc = make_plan(N, &p)) return rc;
+    make_plan(N, &p);
     if (workspace_bytes < p.total) return NPLDA_ENOSPC;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
@@ -351,15 +323,7 @@ int nplda_detcost_sweep_f32(const float* scores, const float* target, int64_t N,
         const int nlabel = (int)((N + 255) / 256 < kLabelBlocks ? (N + 255) / 256 : kLabelBlocks);
         hipLaunchKernelGGL(label_kernel, dim3(nlabel), dim3(256), 0, st, scores, target, (long long)N, keys_in, lab_in, lpart);
         if (int rc = nplda_launch_status()) return rc;
-        size_t tb = p.tmp_bytes;
-        if (hipError_t e = rocprim::radix_sort_pairs(ws + p.o_tmp, tb, (const float*)keys_in, keys,
-                                                     (const unsigned long long*)lab_in,
-                                                     lab, (size_t)N, 0, 32, st))
-            return (int)e;
-        tb = p.tmp_bytes;
-        if (hipError_t e = rocprim::exclusive_scan(ws + p.o_tmp, tb, (const unsigned long long*)lab, pref, 0ull,
-                                                   (size_t)N, rocprim::plus<unsigned long long>(), st))
-            return (int)e;
+        if (int rc = trials::sort_pairs(ws + p.o_tmp, p.tmp_bytes, keys_in, keys, lab_in, lab, pref, (size_t)N, st)) return rc;
         nblocks = (int)((N + 255) / 256 < kSweepBlocks ? (N + 255) / 256 : kSweepBlocks);
         SweepArgs a;
         a.key = keys; a.lab = lab; a.pref = pref; a.lpart = lpart; a.nlabel = nlabel; a.n = N; a.K = K; a.exact = exact ? 1 : 0; a.part = part;

@@ -3,8 +3,8 @@
 // cumulative (trials, targets) diagram of the score bins.
 // Stages, all enqueued on one stream with no read-back (the launch count depends on N alone):
 //   label   scores -> sort keys (an excluded trial or a NaN score gets a positive NaN key: it sorts behind +inf), labels
-//           -> packed (target << 32 | non-target) counts                                          [as nplda_detcost.hip]
-//   sort    rocprim::radix_sort_pairs, then rocprim::exclusive_scan of the packed counts          [as nplda_detcost.hip]
+//           -> packed (target << 32 | non-target) counts                    [nplda_trials.h, policy Excluded::kNanKey]
+//   sort    radix sort of the (key, count) pairs, then the exclusive scan of the packed counts    [trials::sort_pairs]
 //   bins    flag the last trial of every tie run and whether the point after it can be a vertex (pav_flag), scan the
 //           flags, compact the candidates into points (x = trials, y = targets up to there)
 //   hull    level 0: one thread per chunk of kChunk points scans it in place (monotone chain); then ceil(log2(chunks))
@@ -14,25 +14,14 @@
 // The integer logic is csrc/nplda_pav_core.h, shared with the host replay tests/c/pav_core_host.cpp.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
-#include "nplda_common.h"
 #include "nplda_pav_core.h"
+#include "nplda_trials.h"
 
 namespace {
 
 constexpr int kChunk = 32;         // points per level-0 thread
 constexpr int kMaxBlocks = 4096;   // grid cap of the grid-stride kernels
 constexpr double kInv2Ln2 = 0.72134752044448170368;  // 1 / (2 ln 2)
-
-template <class T> struct NanKey;
-template <> struct NanKey<float> {
-    static __device__ __forceinline__ float get() { return __uint_as_float(0x7fc00000u); }
-};
-template <> struct NanKey<double> {
-    static __device__ __forceinline__ double get() { return __longlong_as_double(0x7ff8000000000000ll); }
-};
 
 // y0 + w * d with the product rounded before the sum, as the definition (and a host reference) evaluates it: the
 // compiler's default contraction would fuse the two, and __dmul_rn / __dadd_rn are plain operators to it
@@ -68,12 +57,7 @@ __global__ __launch_bounds__(256) void pav_label_kernel(const T* __restrict__ s,
     long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     for (long long it = 0; it < trips; ++it, i += stride) {
         if (i >= n) return;
-        const T v = s[i];
-        const float l = t[i];
-        unsigned long long code = l > 0.5f ? (1ull << 32) : (l < 0.5f ? 1ull : 0ull);
-        if (v != v) code = 0ull;
-        key[i] = code ? v : NanKey<T>::get();
-        lab[i] = code;
+        trials::key_and_count<trials::Excluded::kNanKey>(s[i], t[i], key[i], lab[i]);
     }
 }
 
@@ -336,29 +320,26 @@ struct Plan {
     int levels;
 };
 
-// rocPRIM's own size queries need a device; the plan must not (it is part of argument checking), so the temporary
-// storage is RESERVED here from N — room for the sort's alternate (key, value) buffers, its per-block digit counters
-// and the scan's look-back states — and the entry point checks rocPRIM's actual request against the reservation.
+// the sort's and the scans' temporary storage is reserved from N, without a device (trials::sort_reserve_bytes)
 void make_plan(long long n, size_t ksz, Plan* p) {
     const size_t nn = (size_t)n;
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     p->maxpts = n + 4;
     p->chunks = pav_hulls(p->maxpts, kChunk, 0);
     p->levels = pav_levels(p->maxpts, kChunk);
     size_t o = 0;
-    p->o_keys_in = o; o += up(nn * ksz);
-    p->o_keys = o; o += up(nn * ksz);
-    p->o_lab_in = o; o += up(nn * 8);  // reused for the bin flags once the sort has read it
-    p->o_lab = o; o += up(nn * 8);
-    p->o_pref = o; o += up(nn * 8);
-    p->o_fpref = o; o += up(nn * 8);
-    p->o_ptsa = o; o += up((size_t)p->maxpts * sizeof(PavPt));
-    p->o_ptsb = o; o += up((size_t)p->maxpts * sizeof(PavPt));
-    p->o_cnta = o; o += up((size_t)p->chunks * sizeof(int));
-    p->o_cntb = o; o += up((size_t)p->chunks * sizeof(int));
-    p->o_br = o; o += up((size_t)pav_hulls(p->maxpts, kChunk, 1) * sizeof(PavBridge));
-    p->o_meta = o; o += up(sizeof(Meta));
-    p->tmp_bytes = up(nn * (ksz + 8) + 2 * nn + ((size_t)4 << 20));
+    p->o_keys_in = o; o += up256(nn * ksz);
+    p->o_keys = o; o += up256(nn * ksz);
+    p->o_lab_in = o; o += up256(nn * 8);  // reused for the bin flags once the sort has read it
+    p->o_lab = o; o += up256(nn * 8);
+    p->o_pref = o; o += up256(nn * 8);
+    p->o_fpref = o; o += up256(nn * 8);
+    p->o_ptsa = o; o += up256((size_t)p->maxpts * sizeof(PavPt));
+    p->o_ptsb = o; o += up256((size_t)p->maxpts * sizeof(PavPt));
+    p->o_cnta = o; o += up256((size_t)p->chunks * sizeof(int));
+    p->o_cntb = o; o += up256((size_t)p->chunks * sizeof(int));
+    p->o_br = o; o += up256((size_t)pav_hulls(p->maxpts, kChunk, 1) * sizeof(PavBridge));
+    p->o_meta = o; o += up256(sizeof(Meta));
+    p->tmp_bytes = trials::sort_reserve_bytes(nn, ksz, 8);
     p->o_tmp = o; o += p->tmp_bytes;
     p->total = o;
 }
@@ -390,38 +371,16 @@ int pav_fit(const T* scores, const float* target, int64_t N, int laplace, double
     int* cnt[2] = {(int*)(ws + p.o_cnta), (int*)(ws + p.o_cntb)};
     PavBridge* br = (PavBridge*)(ws + p.o_br);
     Meta* meta = (Meta*)(ws + p.o_meta);
-    // rocPRIM's requests against the reservation, before anything is enqueued
-    size_t sort_bytes = 0, scan_bytes = 0;
-    if (hipError_t e = rocprim::radix_sort_pairs(nullptr, sort_bytes, (const T*)nullptr, (T*)nullptr,
-                                                 (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                                 (size_t)N, 0, 8 * sizeof(T), st))
-        return (int)e;
-    if (hipError_t e = rocprim::exclusive_scan(nullptr, scan_bytes, (const unsigned long long*)nullptr,
-                                               (unsigned long long*)nullptr, 0ull, (size_t)N,
-                                               rocprim::plus<unsigned long long>(), st))
-        return (int)e;
-    if (sort_bytes > p.tmp_bytes || scan_bytes > p.tmp_bytes) return NPLDA_ENOSPC;
-
     const Grid gn = grid_for(N);
     hipLaunchKernelGGL(pav_label_kernel<T>, dim3(gn.blocks), dim3(256), 0, st, scores, target, (long long)N, gn.trips,
                        keys_in, lab_in);
     if (int rc = nplda_launch_status()) return rc;
-    size_t tb = p.tmp_bytes;
-    if (hipError_t e = rocprim::radix_sort_pairs(ws + p.o_tmp, tb, (const T*)keys_in, keys,
-                                                 (const unsigned long long*)lab_in, lab, (size_t)N, 0, 8 * sizeof(T), st))
-        return (int)e;
-    tb = p.tmp_bytes;
-    if (hipError_t e = rocprim::exclusive_scan(ws + p.o_tmp, tb, (const unsigned long long*)lab, pref, 0ull, (size_t)N,
-                                               rocprim::plus<unsigned long long>(), st))
-        return (int)e;
+    if (int rc = trials::sort_pairs(ws + p.o_tmp, p.tmp_bytes, keys_in, keys, lab_in, lab, pref, (size_t)N, st)) return rc;
     if (stop_after == 1) return NPLDA_OK;
     hipLaunchKernelGGL(pav_flag_kernel<T>, dim3(gn.blocks), dim3(256), 0, st, (const T*)keys,
                        (const unsigned long long*)lab, (const unsigned long long*)pref, (long long)N, gn.trips, 1, flag);
     if (int rc = nplda_launch_status()) return rc;
-    tb = p.tmp_bytes;
-    if (hipError_t e = rocprim::exclusive_scan(ws + p.o_tmp, tb, (const unsigned long long*)flag, fpref, 0ull, (size_t)N,
-                                               rocprim::plus<unsigned long long>(), st))
-        return (int)e;
+    if (int rc = trials::exclusive_scan(ws + p.o_tmp, p.tmp_bytes, flag, fpref, (size_t)N, st)) return rc;
     hipLaunchKernelGGL(pav_point_kernel, dim3(gn.blocks), dim3(256), 0, st, (const unsigned long long*)lab,
                        (const unsigned long long*)pref, (const unsigned long long*)flag, (const unsigned long long*)fpref,
                        (long long)N, gn.trips, laplace ? 1 : 0, pts[0], meta);

@@ -36,8 +36,6 @@ constexpr long long kMaxR = (1ll << 24) - 1;  // the merge is one block of 256 t
 static_assert(kMaxK == NPLDA_TOPK_MAX_K, "the header states the largest k");
 static_assert(kMergeCap >= kMaxK + 64, "a slab of 64 must fit behind the kept k");
 
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct TopkPlan {
     long long nrt, ntiles, tiles_per_chunk;
     int chunks;

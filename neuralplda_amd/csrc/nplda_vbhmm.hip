@@ -27,8 +27,6 @@ constexpr int kSC = 8;  // speakers per thread in the emission phase; alpha^T ro
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // ---- the layout of a problem's workspace slice, in doubles (host and device agree through this one function) -----------------
 
 struct Slice {

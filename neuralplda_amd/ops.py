@@ -1971,18 +1971,25 @@ def dplda_fold_grad(cnt, sm, sq, D1, reduce=None):
     return dw[:-1].float().reshape(1, -1), dw[-1:].float()
 
 
+def _trial_target(target, N, dev):
+    """The labels of N trials for the score-evaluation entry points: fp32, flat, on the device of the scores."""
+    _require_dev_f32(target, "target")
+    t = target.detach().reshape(-1).contiguous()
+    if t.numel() != N or t.device != dev:
+        raise ValueError("target must hold one label per trial, on the device of the scores")
+    return t
+
+
 def detcost_sweep(scores, target, betas, exact=False, want_eer=False):
     """nplda_detcost_sweep_f32 -> (minc (K,), thr (K,), minc_avg (1,), eer (1,) or None), float32 device tensors."""
     lib = _lib.load()
     _require_dev_f32(scores, "scores")
-    _require_dev_f32(target, "target")
-    s, t = scores.detach().reshape(-1).contiguous(), target.detach().reshape(-1).contiguous()
-    if s.numel() != t.numel():
-        raise ValueError("scores and targets must have the same length")
+    s = scores.detach().reshape(-1).contiguous()
+    N = s.numel()
+    t = _trial_target(target, N, s.device)
     K = len(betas)
     if K < 1:
         raise ValueError("at least one beta")
-    N = s.numel()
     nbytes = lib.nplda_detcost_workspace_bytes(N)
     if nbytes == 0:
         raise _lib.NpldaHipError(f"{N} scores are outside the supported range")
@@ -2040,14 +2047,6 @@ def _calib_scores(X, name="scores"):
     return X, N, K, (X.stride(0) if N > 1 else K), sfx
 
 
-def _calib_target(target, N, dev):
-    _require_dev_f32(target, "target")
-    t = target.detach().reshape(-1).contiguous()
-    if t.numel() != N or t.device != dev:
-        raise ValueError("target must hold one label per trial, on the device of the scores")
-    return t
-
-
 def _calib_workspace(lib, N, K, dev):
     nbytes = lib.nplda_calib_workspace_bytes(N, K)
     if nbytes == 0:
@@ -2065,7 +2064,7 @@ def calib_logreg_pass(scores, target, theta, p_target=0.5, l2=0.0):
     (counts (2,) = N_tgt, N_non; J (1,); g (K + 1,); H_upper ((K + 1)(K + 2) / 2,)), device doubles (views of one tensor)."""
     lib = _lib.load()
     X, N, K, ldx, sfx = _calib_scores(scores)
-    t = _calib_target(target, N, X.device)
+    t = _trial_target(target, N, X.device)
     _require_dev_f64(theta, "theta", K + 1, X.device)
     theta = theta.detach().contiguous()
     ws, nbytes = _calib_workspace(lib, N, K, X.device)
@@ -2086,7 +2085,7 @@ def calib_logreg_fit(scores, target, theta, p_target=0.5, l2=0.0, max_passes=64,
     between (one device-to-host copy), so that a fit that converged does not pay for the no-op launches of the rest."""
     lib = _lib.load()
     X, N, K, ldx, sfx = _calib_scores(scores)
-    t = _calib_target(target, N, X.device)
+    t = _trial_target(target, N, X.device)
     _require_dev_f64(theta, "theta", K + 1, X.device)
     if not theta.is_contiguous():
         raise ValueError("theta is updated in place: it must be contiguous")
@@ -2117,7 +2116,7 @@ def calib_gauss_fit(scores, target):
     sfx = _require_dev_float(scores, "scores")
     s = scores.detach().reshape(-1).contiguous()
     N = s.numel()
-    t = _calib_target(target, N, s.device)
+    t = _trial_target(target, N, s.device)
     ws, nbytes = _calib_workspace(lib, N, 1, s.device)
     out = torch.empty(6, dtype=torch.float64, device=s.device)
     with _lib.on_device(s.device):
@@ -2166,7 +2165,7 @@ def calib_costs(llr, target, thresholds=()):
     sfx = _require_dev_float(llr, "llr")
     s = llr.detach().reshape(-1).contiguous()
     N = s.numel()
-    t = _calib_target(target, N, s.device)
+    t = _trial_target(target, N, s.device)
     nth = len(thresholds)
     if nth > 8:
         raise _lib.NpldaHipError("at most 8 thresholds per call")
@@ -2198,7 +2197,7 @@ def pav_fit(scores, target, laplace=True, cap=None):
     sfx = _require_dev_float(scores, "scores")
     s = scores.detach().reshape(-1).contiguous()
     N = s.numel()
-    t = _calib_target(target, N, s.device)
+    t = _trial_target(target, N, s.device)
     cap = min(N + 2, 1 << 16) if cap is None else int(cap)
     if cap < 1:
         raise ValueError("cap must be at least 1")
@@ -2269,7 +2268,7 @@ def bootstrap_metrics(scores, target, g1, G1, g2=None, G2=0, n_boot=1000, seed=0
     _require_dev_f32(scores, "scores")
     s = scores.detach().reshape(-1).contiguous()
     N = s.numel()
-    t = _calib_target(target, N, s.device)
+    t = _trial_target(target, N, s.device)
     g1 = _group_ids(g1, "g1", N, s.device)
     G1, G2 = int(G1), int(G2)
     if g2 is None:

@@ -155,6 +155,22 @@ def with_nans(n, seed, kind):
     return bits.view(F32), t, mask
 
 
+def every_exclusion(n, seed):
+    """One input for all four score-evaluation families: labels from {0, 0.25, 0.5, 0.75, 1, NaN} (42 % in each class, 8 %
+    0.5, 8 % NaN), scores on a grid of 0.25 (ties) with about 2 % each of -inf and +inf and 8 % NaN of both signs, drawn
+    independently of the labels — so every way a trial can leave a class meets every label."""
+    rg = np.random.default_rng(seed)
+    t = np.asarray([0.0, 0.25, 0.5, 0.75, 1.0, np.nan], F32)[rg.choice(6, n, p=[0.32, 0.10, 0.08, 0.10, 0.32, 0.08])]
+    s = (np.round((rg.standard_normal(n) + 1.5 * (t > 0.5)) * 4) / 4).astype(F32)
+    kind = rg.choice(4, n, p=[0.88, 0.02, 0.02, 0.08])
+    s[kind == 1], s[kind == 2] = -np.inf, np.inf
+    bits = s.view(np.uint32).copy()
+    idx = np.flatnonzero(kind == 3)
+    bits[idx[0::2]] = NAN_NEG
+    bits[idx[1::2]] = NAN_POS
+    return bits.view(F32), t
+
+
 NAN_CASES = [(n, kind) for n in (17, 4097) for kind in ("one_target", "one_excluded", "many")]
 
 

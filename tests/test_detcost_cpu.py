@@ -1,6 +1,7 @@
 """The NumPy twin of the detection-cost sweep (tests/detcost_ref.py) against an O(N^2) restatement, the oracle, the
 reference's own outputs on labels outside {0, 1} (golden G5b) and hand-derived answers for every planted case of
-tests/detcost_cases.py — so that a wrong twin cannot pass silently in tests/test_detcost_gpu.py."""
+tests/detcost_cases.py — so that a wrong twin cannot pass silently in tests/test_detcost_gpu.py.  Then the library without
+a device: the workspace size and every status code of nplda_detcost_sweep_f32."""
 import math
 import os
 from fractions import Fraction as Fr
@@ -209,6 +210,19 @@ def test_nan_scores_are_excluded_and_keep_their_label_in_the_normalisers(n, kind
         assert a["minc"][0] == c.min() and a["thr"][0] == st[int(np.argmin(c))]
 
 
+@pytest.mark.parametrize("n", [257, 1025, 4097])
+def test_every_exclusion_keeps_a_quarter_of_the_trials_in_each_class(n):
+    """The input of tests/test_metrics_gpu.py::test_one_trial_rule_in_all_four_families: each way out of a class is planted
+    on each kind of label, and what stays is no corner case."""
+    s, t = cases.every_exclusion(n, n)
+    nan = np.isnan(s)
+    assert {cases.NAN_NEG, cases.NAN_POS} <= set(s.view(np.uint32).tolist()) and (s == np.inf).any() and (s == -np.inf).any()
+    for lab in (t > 0.5, t < 0.5, t == 0.5, np.isnan(t)):
+        assert (lab & nan).any() and (lab & ~nan).any()
+    assert 4 * ((t > 0.5) & ~nan).sum() >= n and 4 * ((t < 0.5) & ~nan).sum() >= n
+    assert np.unique(s[~nan]).size < n // 2  # ties
+
+
 def test_a_nan_cost_never_wins():
     """Only labels of 1: sum (1 - t) = 0, the empty non-target set gives 1.0 / 0 = inf, and beta = 0 makes the cost
     0 * inf = NaN at every threshold: no winner, NaN results (the reference's torch.min would return the NaN too, with
@@ -219,6 +233,45 @@ def test_a_nan_cost_never_wins():
     assert np.isnan(r["minc_avg"])
     minc, thr, avg = ref.brute(s, t, [0.0, 1.0])
     assert same_f32(minc, r["minc"]) and same_f32(thr, r["thr"]) and np.isnan(avg)
+
+
+# ---- the library: planning and argument checking need no device -------------------------------------------------------
+EINVAL, EUNSUPPORTED, ENOSPC = -22, -95, -28
+
+
+def test_workspace_bytes(hip_lib):
+    f = hip_lib.nplda_detcost_workspace_bytes
+    ns = [0, 1, 2, 255, 256, 257, 4099, 1 << 20, 10_000_000, 2 ** 31 - 1]
+    sizes = [f(n) for n in ns]
+    print("nplda_detcost_workspace_bytes", dict(zip(ns, sizes)))
+    assert all(s > 0 for s in sizes) and sizes == sorted(sizes), sizes
+    for n in (-1, 2 ** 31, 2 ** 40):
+        assert f(n) == 0, n
+    # five arrays of N keys, counts and prefixes, and the reservation of N * 14 bytes + 4 MiB for the sort
+    assert 46 * (1 << 20) + (4 << 20) <= f(1 << 20) <= 46 * (1 << 20) + (4 << 20) + (1 << 18)
+
+
+def test_status_codes_of_sweep(hip_lib):
+    """Every code is returned before anything is enqueued: no valid call is made."""
+    import ctypes
+    buf = np.zeros(4096, dtype=np.float64)
+    a = buf.ctypes.data
+    N = 100
+    ws = hip_lib.nplda_detcost_workspace_bytes(N)
+    betas = (ctypes.c_float * 9)(*([1.0] * 9))
+
+    def call(s=a, t=a, N=N, b=betas, K=2, exact=0, minc=a, thr=a, avg=a, eer=a, w=a, wb=ws):
+        return hip_lib.nplda_detcost_sweep_f32(s, t, N, b, K, exact, minc, thr, avg, eer, w, wb, None)
+
+    for name in ("s", "t", "b", "minc", "thr", "avg", "w"):
+        assert call(**{name: None}) == EINVAL, name
+    assert call(w=a + 8) == EINVAL  # not aligned to 16 bytes
+    assert call(N=-1) == EINVAL and call(K=0) == EINVAL and call(K=-2) == EINVAL
+    assert call(K=9) == EUNSUPPORTED and call(N=2 ** 31) == EUNSUPPORTED and call(N=2 ** 40) == EUNSUPPORTED
+    for exact in (0, 1):
+        assert call(exact=exact, wb=ws - 1) == ENOSPC and call(exact=exact, wb=0) == ENOSPC
+    for n in (0, 1):
+        assert call(N=n, wb=hip_lib.nplda_detcost_workspace_bytes(n) - 1) == ENOSPC
 
 
 def test_within_rounding_is_half_an_ulp():

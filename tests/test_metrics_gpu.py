@@ -1,5 +1,6 @@
 """GPU parity of the detection-cost sweep (nplda_detcost_sweep_f32): NeuralPlda.minc with the reference's quirks bit for
-bit (golden G5 = the reference's own outputs), the exact minimum detection cost and the EER against the oracle."""
+bit (golden G5 = the reference's own outputs), the exact minimum detection cost and the EER against the oracle; and the
+rule "which trial counts, and as what" of csrc/nplda_trials.h in the four families that share it."""
 import os
 
 import numpy as np
@@ -54,6 +55,43 @@ def test_sweep_vs_oracle(hip_lib, n, ptgt, quant):
     # determinism
     mc2, th2 = metrics.minc(S, T, betas)
     assert mc2.item() == mc.item() and all(th2[b].item() == th[b].item() for b in betas)
+
+
+@pytest.mark.parametrize("n", [257, 1025])  # one and four label blocks, plus one trial
+def test_one_trial_rule_in_all_four_families(hip_lib, n):
+    """csrc/nplda_trials.h on one input (tests/detcost_cases.py: every_exclusion): target iff t > 0.5, non-target iff
+    t < 0.5, a label of 0.5 or NaN in neither class; the sorted families (detcost, pav, bootstrap) also drop a trial whose
+    score is NaN, the calibration costs do not.  The class counts are NumPy's; the minimum cost is an O(N^2) count over
+    the kept trials in exact integers, which the kernel's single fp64 evaluation meets to half a float32 ulp."""
+    from fractions import Fraction
+
+    from neuralplda_amd import ops
+    from tests import detcost_cases as cases
+    from tests import detcost_ref as ref
+    s, t = cases.every_exclusion(n, n)
+    assert {cases.NAN_NEG, cases.NAN_POS} <= set(s.view(np.uint32).tolist()) and np.isinf(s).any() and np.isnan(t).any()
+    assert all((t == v).any() for v in (0.0, 0.25, 0.5, 0.75, 1.0)) and np.unique(s[~np.isnan(s)]).size < n // 2
+    ok = ~np.isnan(s)
+    tgt, non = (t > 0.5) & ok, (t < 0.5) & ok
+    nt, nn = int(tgt.sum()), int(non.sum())
+    assert 4 * nt >= n and 4 * nn >= n and ((t > 0.5) & ~ok).any() and ((t < 0.5) & ~ok).any()
+    S, T = torch.from_numpy(s).cuda(), torch.from_numpy(t).cuda()
+    summary = ops.pav_fit(S, T)[5].cpu().numpy()
+    g1 = torch.arange(n, dtype=torch.int32, device="cuda") % 7
+    totals = ops.bootstrap_metrics(S, T, g1, 7, n_boot=1)[1].cpu().numpy()
+    counts = ops.calib_costs(S, T)[0].cpu().numpy()
+    beta = 1.0  # an interior threshold wins: at 9 or more, accepting nothing does
+    minc = ops.detcost_sweep(S, T, [beta], exact=True)[0].cpu().numpy()
+    print("pav", summary[:2], "bootstrap", totals[0], "calib", counts, "numpy", nt, nn, "minc", minc)
+    assert summary[0] == nt and summary[1] == nn
+    assert totals[0].tolist() == [nt, nn]
+    assert counts.tolist() == [int((t > 0.5).sum()), int((t < 0.5).sum())]
+    th = np.concatenate([np.unique(s[ok]), [np.inf]])  # every distinct score, then "accept nothing"
+    miss = (tgt[None, :] & (s[None, :] < th[:, None])).sum(axis=1)
+    fa = (non[None, :] & (s[None, :] >= th[:, None])).sum(axis=1)
+    miss[-1], fa[-1] = nt, 0  # the last candidate accepts nothing, a score of +inf included
+    want = min(Fraction(int(m), nt) + int(beta) * Fraction(int(f), nn) for m, f in zip(miss, fa))
+    assert ref.within_rounding(minc[0], want), (minc[0], float(want))
 
 
 def test_sweep_edge_cases(hip_lib):
