@@ -1161,6 +1161,66 @@ int nplda_der_i64(const int64_t* frame_offsets_host, const int64_t* frame_offset
                   const int64_t* item_offsets, const int32_t* item_labels, int64_t* counts, int32_t* map_ref, int32_t* C, void* ws,
                   size_t ws_bytes, nplda_stream_t stream);
 
+/* ---- spectral clustering with an auto-tuned neighbour count (NME-SC) ------------------------------------------ */
+
+/* csrc/nplda_spectral.hip, design/k25_spectral.md.  One call handles P independent PROBLEMS with the conventions of
+ * nplda_ahc_f32: S is the ragged block-diagonal fp32 score matrix of nplda_score_matrix_f32 (problem p's n_p x n_p floats at
+ * element sum_{r < p} n_r^2); only off-diagonal entries are read, -0.0f counts as +0.0f, NaN is outside the contract.
+ * `neighbours` is a HOST table of C candidate neighbour counts, 1 <= C <= 16, positive and strictly increasing.  A CELL is a
+ * (problem, candidate) pair, cell number p C + candidate index.  For a cell with n rows and candidate c, m = min(c, n - 1):
+ *   1. graph: B[i][j] = 1 for the m columns j != i with the largest s_ij, equal scores by ascending j, 0 elsewhere;
+ *      A = (B + B^T) / 2, d_i = sum_j A_ij, L = diag(d) - A: every entry a multiple of 1/2, formed without rounding.
+ *   2. spectrum: all eigenvalues l_1 <= ... <= l_n of L (cyclic Jacobi in float64, round-robin ordering, a rotation skipped
+ *      where |a_pq| <= ||L||_F 2^-53 / (n rounded up to even), at most nplda_spectral_max_sweeps() sweeps, stopping after a
+ *      sweep without a rotation), equal computed values ordered by their position on the diagonal, and the eigenvectors of
+ *      the K + 1 smallest, K = min(max_clusters, n - 1), scaled to unit length.
+ *   3. count: gap_k = l_{k+1} - l_k for min_clusters <= k <= K; k* the k of the largest gap, the lowest among equals;
+ *      g = gap_{k*} / l_n; r = c / g (c, not m), each quotient one correctly rounded division.  Where n <= 1, no k is in
+ *      range, l_n <= 0 or g <= 0: k* = min(min_clusters, max(n, 1)) and r = +inf.
+ *   4. per problem the cell with the smallest r is chosen, the lowest candidate index among equals (so a candidate that
+ *      repeats another after the clip to n - 1 never wins: its g is the same and its c larger).
+ *   5. partition: k = min(k*, n); k-means on the rows of the n x k matrix E of the chosen cell's k smallest eigenvectors.
+ *      Centres: row 0, then each time the row with the largest minimum squared distance to the centres so far (the lowest
+ *      row among equals).  An iteration assigns each row to the nearest centre (the lowest among equals), and, unless that
+ *      assignment repeats the previous iteration's, sets each centre to the mean of its rows (a centre without rows keeps
+ *      its place); it ends at a repeated assignment or after max_iters iterations; n_kmeans_iters counts the assignments made.
+ *      Squared distances (in column order) and centre sums (in row order) are float64, one subtraction, multiplication and
+ *      addition at a time, never contracted; a mean is one division.  Labels: the dense rank of the row's cluster in order
+ *      of the clusters' smallest members; n_clusters: the clusters that own a row.
+ * Outputs, every word written by the call: per cell eigenvalues[max_clusters + 2] (slots 0 .. K the K + 1 smallest, the
+ * last slot l_n, NaN elsewhere and for n = 0), kstar, ratio, n_sweeps, converged (0: the sweep limit was reached; the cell
+ * still takes part); per problem chosen (candidate index), n_clusters, n_kmeans_iters; labels (one int32 per table row).
+ * Optional (NULL: not wanted): embedding (rows x max_clusters doubles; problem p's E, row-major n_p x k, compact at element
+ * offsets[p] max_clusters), degrees (rows x C doubles; cell (p, c)'s d at offsets[p] C + c n_p), vectors (per cell
+ * min(max_clusters + 1, n_p) x n_p doubles, the eigenvectors as ROWS in eigenvalue order, cell after cell).
+ * P == 0 is a no-op; with an empty table only the per-cell and per-problem words are written.
+ * NPLDA_EINVAL: a bad candidate table, min_clusters < 1, max_clusters < min_clusters or > nplda_spectral_max_k(),
+ * max_iters < 1, bad offsets, a null or misaligned pointer.  NPLDA_EUNSUPPORTED: n_p above nplda_spectral_max_n(), P >= 2^22.
+ * NPLDA_ENOSPC: ws_bytes below nplda_spectral_workspace_bytes (0 where the arguments are not acceptable, else a positive
+ * multiple of 256: about 16 n_p^2 bytes per cell).  ws: 16-byte aligned.  Three launches whatever the problems; caller-owned
+ * workspace, nothing allocated, no host synchronisation, capturable, the same bits on every call, no floating-point atomics,
+ * no memset, nothing read back; every error is a status code before any launch. */
+int nplda_spectral_max_n(void);          /* 2048 */
+int nplda_spectral_max_k(void);          /* 64: the speaker slots of the VB-HMM and the DER */
+int nplda_spectral_max_candidates(void); /* 16 */
+int nplda_spectral_max_sweeps(void);     /* 30 */
+int nplda_spectral_block(void);          /* threads of the eigensolver's workgroup (one workgroup per cell) ... */
+int nplda_spectral_small_n(void);        /* ... unless no problem of the call has more rows than this: then ... */
+int nplda_spectral_small_block(void);    /* ... this many */
+size_t nplda_spectral_workspace_bytes(const int64_t* offsets_host, int64_t P, int n_candidates);
+int nplda_spectral_f32(const float* S, const int64_t* offsets_host, const int64_t* offsets, int64_t P, const int32_t* neighbours,
+                       int n_candidates, int min_clusters, int max_clusters, int max_iters, double* eigenvalues, int32_t* kstar,
+                       double* ratio, int32_t* n_sweeps, int32_t* converged, int32_t* chosen, int32_t* n_clusters,
+                       int32_t* n_kmeans_iters, int32_t* labels, double* embedding, double* degrees, double* vectors, void* ws,
+                       size_t ws_bytes, nplda_stream_t stream);
+/* Step 5 alone on caller-given rows: E is (rows, dim) float64, row-major, problem p's rows offsets[p] .. offsets[p + 1];
+ * every problem is partitioned into min(k, n_p) clusters.  1 <= dim, k <= nplda_spectral_max_k(); the other conventions,
+ * limits and status codes as above (workspace: 8 bytes per row). */
+size_t nplda_spectral_kmeans_workspace_bytes(const int64_t* offsets_host, int64_t P);
+int nplda_spectral_kmeans_f64(const double* E, const int64_t* offsets_host, const int64_t* offsets, int64_t P, int dim, int k,
+                              int max_iters, int32_t* n_clusters, int32_t* n_iters, int32_t* labels, void* ws, size_t ws_bytes,
+                              nplda_stream_t stream);
+
 /* ---- measurement utility ------------------------------------------------------------------------------------- */
 
 /* Shader-clock probe for bench.py (no reference counterpart): one wave that stays resident for window_us microseconds

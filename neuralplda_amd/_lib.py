@@ -202,6 +202,17 @@ SIGNATURES = {
     "nplda_vbhmm_workspace_bytes": (_c_sz, [_c_vp, _c_vp, _c_i64, _c_int]),
     "nplda_vbhmm_f64": (_c_int, [_c_f32p, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_vp, _c_vp] +
                         [ctypes.c_double] * 5 + [_c_int] + [_c_vp] * 7 + [_c_sz, _c_vp]),
+    "nplda_spectral_max_n": (_c_int, []),
+    "nplda_spectral_max_k": (_c_int, []),
+    "nplda_spectral_max_candidates": (_c_int, []),
+    "nplda_spectral_max_sweeps": (_c_int, []),
+    "nplda_spectral_block": (_c_int, []),
+    "nplda_spectral_small_n": (_c_int, []),
+    "nplda_spectral_small_block": (_c_int, []),
+    "nplda_spectral_workspace_bytes": (_c_sz, [_c_vp, _c_i64, _c_int]),
+    "nplda_spectral_f32": (_c_int, [_c_f32p, _c_vp, _c_vp, _c_i64, _c_vp] + [_c_int] * 4 + [_c_vp] * 13 + [_c_sz, _c_vp]),
+    "nplda_spectral_kmeans_workspace_bytes": (_c_sz, [_c_vp, _c_i64]),
+    "nplda_spectral_kmeans_f64": (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64] + [_c_int] * 3 + [_c_vp] * 4 + [_c_sz, _c_vp]),
     "nplda_der_max_speakers": (_c_int, []),
     "nplda_der_block": (_c_int, []),
     "nplda_der_workspace_bytes": (_c_sz, [_c_vp, _c_i64]),

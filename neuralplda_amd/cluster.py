@@ -1,5 +1,5 @@
-"""Agglomerative clustering of embeddings under the model's own score (csrc/nplda_ahc.hip, design/k21_ahc.md), and its
-refinement by the Bayesian HMM over each group's rows in time order (VBx: csrc/nplda_vbhmm.hip, design/k22_vbhmm.md).
+"""Agglomerative clustering of embeddings under the model's own score (csrc/nplda_ahc.hip, design/k21_ahc.md), spectral
+clustering with an auto-tuned neighbour count (csrc/nplda_spectral.hip, design/k25_spectral.md), and their refinement by the Bayesian HMM over each group's rows in time order (VBx: csrc/nplda_vbhmm.hip, design/k22_vbhmm.md).
 
 Unlabelled x-vectors become pseudo-speakers: the set is embedded once (search.embed_table), every group of rows (one
 recording, one domain, or the whole set) is one PROBLEM whose dense score matrix ops.score_matrix writes and ops.ahc
@@ -136,6 +136,89 @@ def cluster(model, x, groups=None, threshold=float("-inf"), min_clusters=1, link
     return Clustering(out, n_clusters, rec, offsets, order, n_merges.cpu().numpy())
 
 
+class SpectralClustering:
+    """The result of spectral_cluster(): `labels` (N,) int64 in the CALLER's row order, unique over the whole call (as
+    Clustering), `n_clusters` (P,), `offsets` (P + 1,) and `order` (N,) as in Clustering, `candidates` (C,) the neighbour
+    counts tried, `neighbours` (P,) the count chosen per problem, `chosen` (P,) its index, `eigenvalues` (P, C,
+    max_clusters + 2: the K + 1 smallest of each cell, NaN, the largest in the last slot), `kstar` and `ratio` (P, C),
+    `n_sweeps` (P, C) and `n_kmeans_iters` (P,)."""
+
+    def __init__(self, labels, n_clusters, offsets, order, candidates, chosen, eigenvalues, kstar, ratio, n_sweeps,
+                 n_kmeans_iters):
+        self.labels, self.n_clusters, self.offsets, self.order = labels, n_clusters, offsets, order
+        self.candidates, self.chosen, self.neighbours = candidates, chosen, candidates[chosen]
+        self.eigenvalues, self.kstar, self.ratio, self.n_sweeps = eigenvalues, kstar, ratio, n_sweeps
+        self.n_kmeans_iters = n_kmeans_iters
+
+    def __len__(self):
+        return int(self.labels.shape[0])
+
+    def spk2utt(self, ids, prefix="c"):
+        """As Clustering.spk2utt."""
+        return _spk2utt(self.labels, self.n_clusters, ids, prefix)
+
+
+def _spectral_batches(offsets, C, limit):
+    """Runs of whole problems whose workspace fits `limit` bytes (None: one run) -> [(first problem, end problem), ...]."""
+    P = offsets.size - 1
+    if limit is None or P == 0:
+        return [(0, P)]
+    out, p0 = [], 0
+    while p0 < P:
+        p1 = p0 + 1
+        if ops.spectral_workspace_bytes(offsets[p0:p1 + 1] - offsets[p0], C) > int(limit):
+            raise ValueError(f"workspace_bytes = {int(limit)} does not hold problem {p0} alone "
+                             f"({ops.spectral_workspace_bytes(offsets[p0:p1 + 1] - offsets[p0], C)} bytes)")
+        while p1 < P and ops.spectral_workspace_bytes(offsets[p0:p1 + 2] - offsets[p0], C) <= int(limit):
+            p1 += 1
+        out.append((p0, p1))
+        p0 = p1
+    return out
+
+
+def spectral_cluster(model, x, groups=None, neighbours=None, min_clusters=1, max_clusters=16, workspace_bytes=None,
+                     max_iters=100):
+    """Spectral clustering of the rows of x (as cluster()) under the model's score, each group on its own, with the neighbour
+    count of the affinity graph tuned per group by the normalised maximum eigengap (NME-SC; csrc/nplda_spectral.hip,
+    design/k25_spectral.md) -> SpectralClustering.  No threshold: the number of clusters of a group, between min_clusters
+    and max_clusters, is read from the eigengap.  neighbours: None (ops.SPECTRAL_NEIGHBOURS), a strictly increasing list of
+    candidates, or one int.  workspace_bytes: the groups are worked through in runs of whole groups whose workspace fits
+    (the result does not change by a bit).  Raises where a group's eigensolver did not converge."""
+    if not hasattr(model, "P_sqrt") or not hasattr(model, "centering_and_wccn_plda"):
+        raise NotImplementedError("spectral_cluster scores with the NeuralPlda score (P_sqrt, Q); this model has another head")
+    cand = np.atleast_1d(np.asarray(ops.SPECTRAL_NEIGHBOURS if neighbours is None else neighbours))
+    dev = _search_device(model, x)
+    with torch.no_grad():
+        packed = ops.pack_params(*_model_params(model, dev))
+    z, q = embed_table(model, x, packed)
+    N = z.shape[0]
+    order, offsets = _group_order(groups, N)
+    limit = int(_lib.load().nplda_spectral_max_n())
+    if offsets.size > 1 and int(np.diff(offsets).max()) > limit:
+        raise ValueError(f"a group has {int(np.diff(offsets).max())} rows, spectral_cluster takes at most {limit}")
+    if groups is not None:
+        idx = torch.from_numpy(order).to(dev)
+        z, q = z.index_select(0, idx), q.index_select(0, idx)
+    parts = []
+    for p0, p1 in _spectral_batches(offsets, cand.size, workspace_bytes):
+        r0, r1 = int(offsets[p0]), int(offsets[p1])
+        offs = ops.RaggedOffsets(offsets[p0:p1 + 1] - r0, dev)
+        S = ops.score_matrix(z[r0:r1], q[r0:r1], packed, offs)
+        parts.append(ops.spectral(S, offs, cand, int(min_clusters), int(max_clusters), int(max_iters)))
+    cat = lambda name: torch.cat([getattr(r, name) for r in parts]).cpu().numpy()  # noqa: E731
+    conv = cat("converged")
+    if not conv.all():
+        p, c = np.argwhere(conv == 0)[0]
+        raise _lib.NpldaHipError(f"spectral_cluster: the eigensolver of group {p} (candidate {int(cand[c])}) did not converge "
+                                 f"within {int(_lib.load().nplda_spectral_max_sweeps())} sweeps")
+    n_clusters = cat("n_clusters")
+    base = np.concatenate([[0], np.cumsum(n_clusters)])[:-1]
+    out = np.empty(N, np.int64)
+    out[order] = cat("labels").astype(np.int64) + np.repeat(base, np.diff(offsets))
+    return SpectralClustering(out, n_clusters, offsets, order, cand.astype(np.int64), cat("chosen").astype(np.int64),
+                              cat("eigenvalues"), cat("kstar"), cat("ratio"), cat("n_sweeps"), cat("n_kmeans_iters"))
+
+
 class Refined:
     """The result of vb_refine(): `labels` (N,) int64 in the CALLER's row order, unique over the whole call (the speakers of
     group p follow those of group p - 1; inside a group in order of their slot), `n_clusters` (P,) speakers that own a row,
@@ -159,7 +242,7 @@ def _local_init(init, order, offsets):
     """(labels (N,) int32 in sorted row order and local to each group, S (P,) slots per group) of a Clustering or of an
     integer label array (local per group or global: each group's distinct values are ranked)."""
     N, P = order.size, offsets.size - 1
-    if isinstance(init, Clustering):
+    if isinstance(init, (Clustering, SpectralClustering)):
         if len(init) != N or not np.array_equal(init.offsets, offsets) or not np.array_equal(init.order, order):
             raise ValueError("init must come from cluster() on the same x and groups")
         S = np.asarray(init.n_clusters, np.int64)
@@ -181,7 +264,8 @@ def vb_refine(model, x, init, psi, groups=None, **vb):
     """Refine a clustering of the rows of x by VB-HMM resegmentation (VBx), each group of `groups` on its own -> Refined.
     The rows of a group are taken IN THE CALLER'S ORDER, AND THAT ORDER IS THE TIME ORDER of the HMM: pass the segments of a
     recording in the order they were spoken (groups may interleave; the order inside each group is kept).  `init`: the
-    Clustering that cluster() returned for the same x and groups (over-clustered: its clusters are the speaker slots), or
+    Clustering that cluster() returned for the same x and groups (over-clustered: its clusters are the speaker slots), the
+    SpectralClustering of spectral_cluster(), or
     (N,) integer labels, local per group or global.  `psi`: (D2,) between-class variances of the PLDA model in the space of
     model.extract_plda_embeddings (backend.Backend.psi, kaldi_format.read_plda).  **vb: Fa, Fb, loop_prob, epsilon,
     init_smoothing, max_iters of ops.vbhmm."""

@@ -244,8 +244,8 @@ def read_uem(path, frame_shift=FRAME_SHIFT):
 class Diarization:
     """The result of diarize(): `reco_ids`, `segments` (as speech_segments), `windows` ((W, 4): recording, segment,
     begin, end), `dropped` (segments too short for a window), `xvectors` ((W, 512) on the device), `labels` ((W,) int64,
-    unique over the whole call), `turns` ((N, 4): recording, begin, end, label), and the `clustering` (cluster.Clustering)
-    and `refined` (cluster.Refined or None) they came from."""
+    unique over the whole call), `turns` ((N, 4): recording, begin, end, label), and the `clustering` (cluster.Clustering, or
+    cluster.SpectralClustering under clusterer="spectral") and `refined` (cluster.Refined or None) they came from."""
 
     def __init__(self, reco_ids, segments, windows, dropped, xvectors, labels, turns, clustering, refined):
         self.reco_ids, self.segments, self.windows, self.dropped = reco_ids, segments, windows, dropped
@@ -295,6 +295,9 @@ def sweep_thresholds(diarization, ref_turns, thresholds, reco_ids=None, lengths=
     sweep: the cells score the clustering's cuts, not `refined`."""
     from . import derscore, ops
     clus = diarization.clustering
+    if clus is not None and not hasattr(clus, "cut"):
+        raise ValueError("this diarization was clustered spectrally: there is no dendrogram to cut (diarize with "
+                         'clusterer="ahc" to sweep thresholds)')
     thresholds = [float(t) for t in np.asarray(thresholds, np.float64).reshape(-1)]
     if not thresholds or any(t != t for t in thresholds):
         raise ValueError("give at least one threshold, none of them NaN")
@@ -357,7 +360,7 @@ def sweep_thresholds(diarization, ref_turns, thresholds, reco_ids=None, lengths=
 
 def diarize(model, extractor, frames, lengths, reco_ids, segments=None, vad=features.VadOptions(), min_speech=50,
             max_gap=30, cmn_window=300, window=144, shift=24, min_frames=CONTEXT + 2, threshold=0.0, min_clusters=1,
-            linkage="average", vb_psi=None, vb=None, workspace_bytes=None):
+            linkage="average", vb_psi=None, vb=None, workspace_bytes=None, clusterer="ahc", spectral=None):
     """Diarize whole recordings -> Diarization.  frames: (sum T_r, 30) raw MFCC rows on the device, recording r being the
     next lengths[r] rows; reco_ids: their names.  The steps, all on the device but the window bookkeeping:
       1. segments: the given ones (the structure of speech_segments), or features.energy_vad(vad) through
@@ -366,7 +369,9 @@ def diarize(model, extractor, frames, lengths, reco_ids, segments=None, vad=feat
          stay aligned with time;
       3. uniform_windows(window, shift, min_frames);
       4. extractor.extract_windows over the windows' rows (an XVectorNet_ETDNN_12Layer);
-      5. cluster.cluster(model, x-vectors, groups=recording, threshold, min_clusters, linkage);
+      5. cluster.cluster(model, x-vectors, groups=recording, threshold, min_clusters, linkage); or, with
+         clusterer="spectral", cluster.spectral_cluster(model, x-vectors, groups=recording, **spectral) (spectral: a dict of
+         its neighbours, min_clusters, max_clusters, workspace_bytes; threshold, min_clusters and linkage are not used);
       6. with vb_psi (the PLDA between-class variances): cluster.vb_refine(model, x-vectors, that clustering, vb_psi,
          groups=recording, **vb); a recording's windows are in time order already;
       7. turns()."""
@@ -374,6 +379,10 @@ def diarize(model, extractor, frames, lengths, reco_ids, segments=None, vad=feat
     reco_ids = list(reco_ids)
     if len(reco_ids) != len(lengths):
         raise ValueError(f"{len(reco_ids)} recording names, {len(lengths)} lengths")
+    if clusterer not in ("ahc", "spectral"):
+        raise ValueError('clusterer must be "ahc" or "spectral"')
+    if spectral is not None and clusterer != "spectral":
+        raise ValueError('spectral= holds the options of clusterer="spectral"')
     if segments is None:
         segments = speech_segments(features.energy_vad(frames, lengths, vad), lengths, min_speech, max_gap)
     elif len(segments) != len(lengths):
@@ -392,7 +401,10 @@ def diarize(model, extractor, frames, lengths, reco_ids, segments=None, vad=feat
     labels = np.zeros(0, np.int64)
     if windows.shape[0]:
         groups = windows[:, 0]
-        clus = cluster.cluster(model, x, groups=groups, threshold=threshold, min_clusters=min_clusters, linkage=linkage)
+        if clusterer == "spectral":
+            clus = cluster.spectral_cluster(model, x, groups=groups, **(spectral or {}))
+        else:
+            clus = cluster.cluster(model, x, groups=groups, threshold=threshold, min_clusters=min_clusters, linkage=linkage)
         labels = clus.labels
         if vb_psi is not None:
             refined = cluster.vb_refine(model, x, clus, vb_psi, groups=groups, **(vb or {}))

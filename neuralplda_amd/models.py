@@ -571,6 +571,13 @@ class NeuralPlda(nn.Module):
         from . import cluster
         return cluster.cluster(self, x, groups=groups, threshold=threshold, min_clusters=min_clusters, linkage=linkage)
 
+    def spectral_cluster(self, x, groups=None, neighbours=None, min_clusters=1, max_clusters=16, workspace_bytes=None):
+        """Spectral clustering of the rows of x under this model's score with the neighbour count tuned per group by the
+        normalised maximum eigengap, each group on its own -> cluster.SpectralClustering (labels, .spk2utt): no threshold."""
+        from . import cluster
+        return cluster.spectral_cluster(self, x, groups=groups, neighbours=neighbours, min_clusters=min_clusters,
+                                        max_clusters=max_clusters, workspace_bytes=workspace_bytes)
+
     def vb_refine(self, x, init, psi, **kw):
         """VB-HMM resegmentation (VBx) of a clustering of the rows of x, each group's rows in time order ->
         cluster.Refined (cluster.vb_refine)."""
@@ -707,6 +714,10 @@ class DPlda(NeuralPlda):
     def cluster(self, x, **kw):
         raise NotImplementedError("cluster scores with the NeuralPlda score (P_sqrt, Q); DPlda has a quadratic-form head")
 
+    def spectral_cluster(self, x, **kw):
+        raise NotImplementedError("spectral_cluster scores with the NeuralPlda score (P_sqrt, Q); DPlda has a quadratic-form "
+                                  "head")
+
     def vb_refine(self, x, init, psi, **kw):
         raise NotImplementedError("vb_refine works on the NeuralPlda embeddings (P_sqrt, Q); DPlda has a quadratic-form head")
 
@@ -791,6 +802,10 @@ class GaussianBackend(nn.Module):
     def cluster(self, x, **kw):
         raise NotImplementedError("cluster scores with the NeuralPlda score (P_sqrt, Q); the Gaussian back end scores a pair "
                                   "from its paired statistics")
+
+    def spectral_cluster(self, x, **kw):
+        raise NotImplementedError("spectral_cluster scores with the NeuralPlda score (P_sqrt, Q); the Gaussian back end "
+                                  "scores a pair from its paired statistics")
 
     def vb_refine(self, x, init, psi, **kw):
         raise NotImplementedError("vb_refine works on the NeuralPlda embeddings (P_sqrt, Q); the Gaussian back end scores a "

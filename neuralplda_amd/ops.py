@@ -1355,6 +1355,148 @@ def ahc(S, offsets=None, linkage="average", threshold=float("-inf"), min_cluster
     return merges, n_merges, n_clusters, labels
 
 
+SPECTRAL_NEIGHBOURS = (2, 3, 4, 6, 8, 12, 16, 24, 32, 48)  # the default candidate ladder (design/k25_spectral.md)
+
+
+class SpectralResult:
+    """What spectral() wrote, all on the device: per cell `eigenvalues` (P, C, max_clusters + 2), `kstar`, `n_sweeps`,
+    `converged` (P, C) int32 and `ratio` (P, C) float64; per problem `chosen`, `n_clusters`, `n_kmeans_iters` (P,) int32;
+    `labels` (rows,) int32; and, where asked for, `embedding` (rows, max_clusters) float64 (problem p's n x k matrix compact
+    at row offsets[p]: see embedding_of), `degrees` (flat, cell (p, c) at offsets[p] C + c n_p) and `vectors` (flat, see
+    vectors_of)."""
+
+    __slots__ = ("eigenvalues", "kstar", "ratio", "n_sweeps", "converged", "chosen", "n_clusters", "n_kmeans_iters", "labels",
+                 "embedding", "degrees", "vectors", "offsets", "neighbours", "max_clusters")
+
+    def k_of(self, p):
+        """Columns of problem p's embedding: min(k* of the chosen cell, n_p) (reads two words back)."""
+        n = int(self.offsets[p + 1] - self.offsets[p])
+        return min(int(self.kstar[p, int(self.chosen[p])]), n)
+
+    def embedding_of(self, p):
+        """Problem p's (n_p, k) embedding (a view)."""
+        r0, n, k = int(self.offsets[p]), int(self.offsets[p + 1] - self.offsets[p]), self.k_of(p)
+        return self.embedding.view(-1)[r0 * self.max_clusters:r0 * self.max_clusters + n * k].view(n, k)
+
+    def degrees_of(self, p, c):
+        r0, n, C = int(self.offsets[p]), int(self.offsets[p + 1] - self.offsets[p]), len(self.neighbours)
+        return self.degrees[r0 * C + c * n:r0 * C + (c + 1) * n]
+
+    def vectors_of(self, p, c):
+        """Cell (p, c)'s eigenvectors as ROWS, (min(max_clusters + 1, n_p), n_p), in eigenvalue order (a view)."""
+        import numpy as np
+        n = np.diff(self.offsets)
+        rows = np.minimum(self.max_clusters + 1, n)
+        C = len(self.neighbours)
+        base = int((C * rows[:p] * n[:p]).sum()) + c * int(rows[p] * n[p])
+        return self.vectors[base:base + int(rows[p] * n[p])].view(int(rows[p]), int(n[p]))
+
+
+def _spectral_table(neighbours, lib):
+    import numpy as np
+    nb = np.atleast_1d(np.asarray(neighbours))
+    if nb.ndim != 1 or nb.dtype.kind not in "iu" or not 1 <= nb.size <= lib.nplda_spectral_max_candidates() or \
+            (nb < 1).any() or (nb >= 2 ** 31).any() or (np.diff(nb) <= 0).any():
+        raise ValueError(f"neighbours must be 1 .. {lib.nplda_spectral_max_candidates()} positive, strictly increasing integers")
+    return np.ascontiguousarray(nb.astype(np.int32))
+
+
+def spectral_workspace_bytes(offsets, n_candidates):
+    """nplda_spectral_workspace_bytes for host offsets (any sequence) and a candidate count; 0 where they are not acceptable."""
+    import numpy as np
+    host = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    return int(_lib.load().nplda_spectral_workspace_bytes(host.ctypes.data, host.size - 1, int(n_candidates)))
+
+
+def spectral(S, offsets=None, neighbours=SPECTRAL_NEIGHBOURS, min_clusters=1, max_clusters=None, max_iters=100,
+             return_embedding=False, return_degrees=False, return_vectors=False):
+    """nplda_spectral_f32: spectral clustering of every problem under its float32 score matrix in S (the layout of
+    score_matrix) with the neighbour count chosen per problem among `neighbours` by the normalised maximum eigengap
+    (include/nplda_hip.h has the definitions) -> SpectralResult.  max_clusters None: nplda_spectral_max_k().  Nothing is read
+    back: a cell whose eigensolver stopped at its sweep limit has converged == 0 (cluster.spectral_cluster raises on it)."""
+    lib = _lib.load()
+    _require_dev_f32(S, "S")
+    nb = _spectral_table(neighbours, lib)
+    limit = int(lib.nplda_spectral_max_k())
+    min_clusters, max_iters = int(min_clusters), int(max_iters)
+    max_clusters = limit if max_clusters is None else int(max_clusters)
+    if min_clusters < 1 or not min_clusters <= max_clusters <= limit or max_iters < 1:
+        raise ValueError(f"need 1 <= min_clusters <= max_clusters <= {limit} and max_iters >= 1")
+    if not S.is_contiguous():
+        S = S.contiguous()
+    dev = S.device
+    if offsets is None:
+        if S.dim() != 2 or S.shape[0] != S.shape[1]:
+            raise ValueError("without offsets S must be one square matrix")
+        offsets = [0, S.shape[0]]
+    offs = _ragged(offsets, 0, dev)
+    if S.numel() != offs.elems:
+        raise ValueError(f"S holds {S.numel()} scores, the offsets ask for {offs.elems}")
+    if offs.P and int((offs.host[1:] - offs.host[:-1]).max()) > lib.nplda_spectral_max_n():
+        raise ValueError(f"a problem may have at most {lib.nplda_spectral_max_n()} rows")
+    import numpy as np
+    P, C, n = offs.P, int(nb.size), offs.host[1:] - offs.host[:-1]
+    out = SpectralResult()
+    out.offsets, out.neighbours, out.max_clusters = offs.host, nb, max_clusters
+    out.eigenvalues = torch.empty((P, C, max_clusters + 2), dtype=torch.float64, device=dev)
+    out.ratio = torch.empty((P, C), dtype=torch.float64, device=dev)
+    out.kstar, out.n_sweeps, out.converged = (torch.empty((P, C), dtype=torch.int32, device=dev) for _ in range(3))
+    out.chosen, out.n_clusters, out.n_kmeans_iters = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
+    out.labels = torch.empty(offs.rows, dtype=torch.int32, device=dev)
+    out.embedding = torch.empty((offs.rows, max_clusters), dtype=torch.float64, device=dev) if return_embedding else None
+    out.degrees = torch.empty(offs.rows * C, dtype=torch.float64, device=dev) if return_degrees else None
+    out.vectors = torch.empty(int((C * np.minimum(max_clusters + 1, n) * n).sum()), dtype=torch.float64, device=dev) \
+        if return_vectors else None
+    if P == 0:
+        return out
+    wsb = lib.nplda_spectral_workspace_bytes(offs.hptr, P, C)
+    if wsb == 0:
+        raise _lib.NpldaHipError("spectral: the offsets are outside what the kernel takes")
+    ws = torch.empty(wsb // 8 if offs.rows else 2, dtype=torch.float64, device=dev)
+    with _lib.on_device(dev):
+        code = lib.nplda_spectral_f32(_lib.ptr(S), offs.hptr, _lib.ptr(offs.dev), P, nb.ctypes.data, C, min_clusters,
+                                      max_clusters, max_iters, _lib.ptr(out.eigenvalues), _lib.ptr(out.kstar),
+                                      _lib.ptr(out.ratio), _lib.ptr(out.n_sweeps), _lib.ptr(out.converged), _lib.ptr(out.chosen),
+                                      _lib.ptr(out.n_clusters), _lib.ptr(out.n_kmeans_iters), _lib.ptr(out.labels),
+                                      _lib.ptr(out.embedding), _lib.ptr(out.degrees), _lib.ptr(out.vectors), _lib.ptr(ws),
+                                      ws.numel() * 8, _lib.current_stream())
+    _lib.check(code, "nplda_spectral_f32")
+    return out
+
+
+def spectral_kmeans(E, offsets=None, k=2, max_iters=100):
+    """nplda_spectral_kmeans_f64: the k-means of spectral() on caller-given rows.  E: (rows, dim) float64 on the device, each
+    problem's rows partitioned into min(k, n_p) clusters -> (labels (rows,), n_clusters (P,), n_iters (P,)), int32 on the
+    device."""
+    lib = _lib.load()
+    if not isinstance(E, torch.Tensor) or not E.is_cuda or E.dtype != torch.float64 or E.dim() != 2:
+        raise TypeError("E must be a (rows, dim) float64 tensor on a HIP device")
+    limit = int(lib.nplda_spectral_max_k())
+    k, max_iters = int(k), int(max_iters)
+    if not 1 <= E.shape[1] <= limit or not 1 <= k <= limit or max_iters < 1:
+        raise ValueError(f"need 1 <= dim <= {limit}, 1 <= k <= {limit} and max_iters >= 1")
+    E = E.contiguous()
+    dev, rows, dim = E.device, E.shape[0], E.shape[1]
+    offs = _ragged(offsets, rows, dev)
+    if offs.rows != rows:
+        raise ValueError(f"the offsets cover {offs.rows} rows, E has {rows}")
+    if offs.P and int((offs.host[1:] - offs.host[:-1]).max()) > lib.nplda_spectral_max_n():
+        raise ValueError(f"a problem may have at most {lib.nplda_spectral_max_n()} rows")
+    labels = torch.empty(rows, dtype=torch.int32, device=dev)
+    n_clusters = torch.empty(offs.P, dtype=torch.int32, device=dev)
+    n_iters = torch.empty(offs.P, dtype=torch.int32, device=dev)
+    if offs.P == 0:
+        return labels, n_clusters, n_iters
+    wsb = lib.nplda_spectral_kmeans_workspace_bytes(offs.hptr, offs.P)
+    ws = torch.empty(max(wsb // 8, 2), dtype=torch.float64, device=dev)
+    with _lib.on_device(dev):
+        code = lib.nplda_spectral_kmeans_f64(_lib.ptr(E), offs.hptr, _lib.ptr(offs.dev), offs.P, dim, k, max_iters,
+                                             _lib.ptr(n_clusters), _lib.ptr(n_iters), _lib.ptr(labels), _lib.ptr(ws),
+                                             ws.numel() * 8, _lib.current_stream())
+    _lib.check(code, "nplda_spectral_kmeans_f64")
+    return labels, n_clusters, n_iters
+
+
 def vbhmm(z, offsets, spk_offsets, psi, labels_init=None, gamma_init=None, pi_init=None, Fa=0.3, Fb=17.0, loop_prob=0.99,
           epsilon=1e-4, init_smoothing=5.0, max_iters=40):
     """nplda_vbhmm_f64: VB-HMM resegmentation (VBx) of P problems over one table, all in float64 on the device.  z: (rows, ld)

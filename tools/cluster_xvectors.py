@@ -20,6 +20,10 @@ variances must belong to the space of the model's embeddings; the utterances of 
 above the expected number of speakers (at most 64 clusters per recording): the clusters are the speaker slots the
 refinement starts from.  --vb-fa, --vb-fb, --vb-loop, --vb-max-iters: its scaling factors, self-loop probability and
 iteration limit.
+--method spectral: spectral clustering with the neighbour count of the affinity graph tuned per recording by the normalised
+maximum eigengap instead (cluster.spectral_cluster; at most 2 048 rows per recording): no threshold; --neighbours 4,6,8,...
+gives the candidate counts, --max-speakers the most clusters per recording (default 16), --min-clusters the fewest;
+--threshold, --calibration and --linkage are not used.
 Output: `utt2spk` (sorted by utterance) and `spk2utt` in --out-dir, what every spk2utt consumer of the package reads."""
 import argparse
 import os
@@ -43,6 +47,9 @@ def main(argv=None):
                     help="--threshold is in units of llr = A s + B (A > 0): it is mapped to (threshold - B) / A")
     ap.add_argument("--min-clusters", type=int, default=1)
     ap.add_argument("--linkage", default="average", choices=["average", "complete", "single"])
+    ap.add_argument("--method", default="ahc", choices=["ahc", "spectral"])
+    ap.add_argument("--neighbours", help="--method spectral: comma-separated candidate neighbour counts, strictly increasing")
+    ap.add_argument("--max-speakers", type=int, default=16, help="--method spectral: the most clusters per recording")
     ap.add_argument("--vb-plda", help="a Kaldi PLDA model: refine the clusters by VB-HMM resegmentation under its psi")
     ap.add_argument("--vb-fa", type=float, default=0.3)
     ap.add_argument("--vb-fb", type=float, default=17.0)
@@ -75,7 +82,12 @@ def main(argv=None):
         x = table.on(dev)[torch.from_numpy(rows).to(dev)]
     else:
         groups, ids, x = None, list(table.ids), table.on(dev)
-    res = cluster.cluster(model, x, groups=groups, threshold=thr, min_clusters=args.min_clusters, linkage=args.linkage)
+    if args.method == "spectral":
+        nb = [int(v) for v in args.neighbours.split(",")] if args.neighbours else None
+        res = cluster.spectral_cluster(model, x, groups=groups, neighbours=nb, min_clusters=args.min_clusters,
+                                       max_clusters=args.max_speakers)
+    else:
+        res = cluster.cluster(model, x, groups=groups, threshold=thr, min_clusters=args.min_clusters, linkage=args.linkage)
     if args.vb_plda:
         from neuralplda_amd import kaldi_format
         psi = kaldi_format.read_plda(args.vb_plda)["Psi_across_covar_diag"]

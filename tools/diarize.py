@@ -16,6 +16,9 @@ recording it does not list has no speech.  Without it the energy VAD of the pack
 --window / --shift (frames): the rule of neuralplda_amd.diarize.uniform_windows.
 --threshold, --calibration, --min-clusters, --linkage, --vb-plda, --vb-fa, --vb-fb, --vb-loop, --vb-max-iters: the
 clustering and the VB-HMM resegmentation, as in tools/cluster_xvectors.py (each recording on its own).
+--clusterer spectral [--neighbours 4,6,8,...] [--max-speakers N]: cluster.spectral_cluster in place of the agglomerative
+step: no threshold, the speaker count of a recording (between --min-clusters and --max-speakers, default 16) comes from the
+eigengap of its affinity graph; the VB-HMM options apply as before.
 The scp is worked through --recordings-per-call recordings at a time, so that the features and the workspaces stay
 bounded; speaker labels are counted on through the pieces.  Output: one RTTM line per speaker turn.
 --ref-rttm: a reference RTTM; the overall diarization error rate of the output against it (collar 0.25 s, overlapped
@@ -68,6 +71,11 @@ def main(argv=None):
                     help="--threshold is in units of llr = A s + B (A > 0): it is mapped to (threshold - B) / A")
     ap.add_argument("--min-clusters", type=int, default=1)
     ap.add_argument("--linkage", default="average", choices=["average", "complete", "single"])
+    ap.add_argument("--clusterer", default="ahc", choices=["ahc", "spectral"],
+                    help="spectral: the neighbour count of the affinity graph is tuned per recording by the normalised maximum "
+                         "eigengap and the speaker count read from it; --threshold, --calibration and --linkage are not used")
+    ap.add_argument("--neighbours", help="--clusterer spectral: comma-separated candidate neighbour counts, strictly increasing")
+    ap.add_argument("--max-speakers", type=int, default=16, help="--clusterer spectral: the most speakers per recording")
     ap.add_argument("--vb-plda", help="a Kaldi PLDA model: refine the clusters by VB-HMM resegmentation under its psi")
     ap.add_argument("--vb-fa", type=float, default=0.3)
     ap.add_argument("--vb-fb", type=float, default=17.0)
@@ -93,6 +101,10 @@ def main(argv=None):
     extractor, model = load_extractor(args.xvector_model, dev), load_model(args.model, dev)
     psi = kaldi_format.read_plda(args.vb_plda)["Psi_across_covar_diag"] if args.vb_plda else None
     vb = dict(Fa=args.vb_fa, Fb=args.vb_fb, loop_prob=args.vb_loop, max_iters=args.vb_max_iters)
+    spectral = None
+    if args.clusterer == "spectral":
+        spectral = dict(neighbours=[int(v) for v in args.neighbours.split(",")] if args.neighbours else None,
+                        min_clusters=args.min_clusters, max_clusters=args.max_speakers)
     given = None
     if args.segments:
         recs, segs = diarize.read_segments(args.segments, args.frame_shift)
@@ -119,7 +131,8 @@ def main(argv=None):
             segments = [np.minimum(given.get(k, np.zeros((0, 2), np.int64)), T) for k, T in zip(keys, lengths)]
         res = diarize.diarize(model, extractor, frames, lengths, keys, segments=segments, min_speech=args.min_speech,
                               max_gap=args.max_gap, cmn_window=args.cmn_window, window=args.window, shift=args.shift,
-                              threshold=thr, min_clusters=args.min_clusters, linkage=args.linkage, vb_psi=psi, vb=vb)
+                              threshold=thr, min_clusters=args.min_clusters, linkage=args.linkage, vb_psi=psi, vb=vb,
+                              clusterer=args.clusterer, spectral=spectral)
         for r, s, n in res.dropped:
             print(f"diarize: {keys[r]}: a segment of {n} frames is too short for a window", file=sys.stderr)
         t = res.turns.copy()
