@@ -237,6 +237,44 @@ int nplda_allpairs_loss_f32(const float* z, int64_t ldz, int64_t N, int D2, cons
                             float alpha, int kind, double* sums, float* loss, float* dtheta, float* dz, int64_t lddz,
                             float* dP_sqrt, float* dQ, void* ws, size_t ws_bytes, nplda_stream_t stream);
 
+/* ---- speaker-classification loss over a class table (csrc/nplda_classify.hip, design/k26_classify.md) ----------- */
+
+/* Bytes of caller-provided workspace nplda_classify_loss_f32 needs for N rows, C classes and D features under the chunk
+ * arguments it will be called with (0 = the plan's choice, a function of (N, C, D) alone): the padded images of X and W,
+ * per-row and per-class vectors, and one partial of the gradients per chunk — nothing grows with N * C.  Never decreases
+ * with N or C.  0 for N or C outside 0 .. 2^20, D outside 1 .. nplda_max_dim() or a negative chunk argument. */
+size_t nplda_classify_workspace_bytes(int64_t N, int64_t C, int D, int class_chunks, int row_chunks);
+
+/* Softmax (kind 0), AM-softmax / CosFace (kind 1) or AAM-softmax / ArcFace (kind 2) cross entropy of N embeddings
+ * X (N, ldx) against a class table W (C, ldw) with optional bias b (C) and labels y (N int32), scale s > 0, margin m >= 0,
+ * with every gradient; the N x C logits are never written.
+ *   kind 0: u_ic = <x_i, w_c> (m must be 0);  kinds 1, 2: u_ic = <x^_i, w^_c>, x^_i = x_i / max(||x_i||, 1e-12), w^_c likewise
+ *   a_ic = s u_ic + b_c (the inference logit);  l_ic = a_ic for c != y_i,  l_iy = s phi(u_iy) + b_y (the training logit)
+ *   phi(u) = u (kind 0), u - m (kind 1); kind 2: v = clamp(u, -1, 1), sn = sqrt(max(1 - v^2, 2^-24)),
+ *     v > -cos m: phi = v cos m - sn sin m, phi' = cos m + (v / sn) sin m;  otherwise phi = v - m sin m, phi' = 1
+ *     (the clamp is the identity in the derivative)
+ *   V = {i: 0 <= y_i < C}: y_i = -1 ignores row i; any other label outside 0 .. C - 1 is ignored too, and counted
+ *   lse_i = log sum_c exp(l_ic);  rowloss_i = lse_i - l_iy on V, 0 elsewhere;  loss = sum_{i in V} rowloss_i / |V| (fp64 sum,
+ *     rows in order; NaN for an empty V);  pred_i = argmax_c a_ic for every row (margin-free, the lowest index on ties)
+ *   counts (3 int64) = |V|, #{i in V: pred_i = y_i}, #{i: y_i < -1 or y_i >= C}
+ *   g_ic = (exp(l_ic - lse_i) - [c = y_i]) / |V| on V, 0 elsewhere;  db_c = sum_i g_ic;  h_ic = s g_ic, times phi'(u_iy) at c = y_i
+ *   kind 0: dX = H W, dW = H^T X;  kinds 1, 2: A = H W^, dX_i = (A_i - <x^_i, A_i> x^_i) / max(||x_i||, 1e-12), and dW the
+ *     same way from H^T X^.
+ * rowloss (N), pred (N int32), dX (N, lddx), dW (C, lddw) and db (C) may each be NULL; without dX the rows-own gradient pass is
+ * not launched, without dW and db the classes-own pass is not, without any of the three only the loss passes run.
+ * class_chunks / row_chunks: into how many chunks the class tiles (of 16) / row tiles (of 16) are split over blocks; 0 = the
+ * plan's choice, a positive value is used as given (at most one chunk per tile, at most 1024): the results agree to rounding,
+ * pred and counts exactly away from ties in fp32.  Kernel launches on `stream` and nothing else (no allocation, no memset, no synchronisation:
+ * capturable); bitwise repeatable for one (shape, chunk arguments): fixed summation orders, no floating-point atomics.
+ * N == 0 or C == 0: nothing is launched, NPLDA_OK.  NPLDA_EINVAL: a null required pointer (X, W, y, loss, counts, ws), X / W /
+ * dX / dW / ws not 16-byte aligned, ldx / ldw / lddx / lddw below D or not a multiple of 4, kind outside 0 .. 2, s <= 0, m < 0,
+ * m != 0 under kind 0, m >= pi under kind 2, N, C or a chunk argument negative, D <= 0; NPLDA_EUNSUPPORTED: D above
+ * nplda_max_dim(), N or C above 2^20; NPLDA_ENOSPC: ws_bytes below nplda_classify_workspace_bytes of the same arguments. */
+int nplda_classify_loss_f32(const float* X, int64_t ldx, int64_t N, const float* W, int64_t ldw, int64_t C, int D,
+                            const float* b, const int32_t* y, int kind, float s, float m, int class_chunks, int row_chunks,
+                            float* loss, int64_t* counts, float* rowloss, int32_t* pred, float* dX, int64_t lddx, float* dW,
+                            int64_t lddw, float* db, void* ws, size_t ws_bytes, nplda_stream_t stream);
+
 /* ---- top-k search over an embedding table (csrc/nplda_topk.hip, design/k19_topk_search.md) ---------------------- */
 
 /* Largest k of nplda_topk_scores_f32. */

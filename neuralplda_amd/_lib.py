@@ -183,6 +183,10 @@ SIGNATURES = {
                                          ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_float), _c_int,
                                          ctypes.c_float, _c_int, _c_vp, _c_f32p, _c_f32p, _c_f32p, _c_i64, _c_f32p, _c_f32p,
                                          _c_vp, _c_sz, _c_vp]),
+    "nplda_classify_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_int, _c_int, _c_int]),
+    "nplda_classify_loss_f32": (_c_int, [_c_f32p, _c_i64, _c_i64, _c_f32p, _c_i64, _c_i64, _c_int, _c_f32p, _c_vp, _c_int,
+                                         ctypes.c_float, ctypes.c_float, _c_int, _c_int, _c_f32p, _c_vp, _c_f32p, _c_vp,
+                                         _c_f32p, _c_i64, _c_f32p, _c_i64, _c_f32p, _c_vp, _c_sz, _c_vp]),
     "nplda_topk_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_int, _c_int]),
     "nplda_topk_scores_f32": (_c_int, [_c_f32p, _c_f32p, _c_i64, _c_f32p, _c_f32p, _c_i64, _c_i64, _c_vp, _c_int, _c_int,
                                        _c_int, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_f32p, _c_vp,

@@ -383,6 +383,70 @@ class _AllPairsLossFn(torch.autograd.Function):
                 _back(dP * gl, P_sqrt) if need[7] else None, _back(dQ * gl, Q) if need[8] else None) + tuple(dths)
 
 
+class _ClassifyLossFn(torch.autograd.Function):
+    """Softmax / AM / AAM cross entropy of the embeddings z (N, D) against a class table (ops.classify_loss).  The gradients
+    of z, the table and the bias come out of the forward's one call and are scaled by the incoming gradient in backward, as
+    _AllPairsLossFn does.  Returns (loss, counts, pred); the last two carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, z, labels, opts, weight, bias):
+        kind, scale, margin, grad_on = opts
+        dev = _compute_device(z, weight)
+        Z, Wd = _to_dev(z, dev), _to_dev(weight, dev)
+        bd = None if bias is None else _to_dev(bias, dev)
+        need_x = grad_on and ctx.needs_input_grad[0]
+        need_w = grad_on and (ctx.needs_input_grad[3] or (bias is not None and ctx.needs_input_grad[4]))
+        r = ops.classify_loss(Z, labels, Wd, bd, kind=kind, scale=scale, margin=margin, want_dx=need_x, want_dw=need_w)
+        ctx.need = need_x or need_w
+        ctx.has = (r.dx is not None, r.dw is not None, r.db is not None)
+        ctx.has_bias = bias is not None
+        if ctx.need:
+            ctx.save_for_backward(*[t for t in (r.dx, r.dw, r.db) if t is not None], z, weight,
+                                  *(() if bias is None else (bias,)))
+        ctx.mark_non_differentiable(r.counts, r.pred)
+        return (r.loss if r.loss.device == z.device else r.loss.to(z.device)), r.counts, r.pred
+
+    @staticmethod
+    def backward(ctx, gl, _gc, _gp):
+        if not ctx.need:
+            return (None,) * 5
+        saved = list(ctx.saved_tensors)
+        dx, dw, db = (saved.pop(0) if h else None for h in ctx.has)
+        z, weight = saved[0], saved[1]
+        bias = saved[2] if ctx.has_bias else None
+        gl = gl.to((dx if dx is not None else dw).device)
+        need = ctx.needs_input_grad
+        return (_back(dx * gl, z) if need[0] and dx is not None else None, None, None,
+                _back(dw * gl, weight) if need[3] and dw is not None else None,
+                _back(db * gl, bias) if bias is not None and need[4] and db is not None else None)
+
+
+class SpeakerClassifier(nn.Module):
+    """A speaker-classification head on embeddings: a class table `weight` (num_classes, dim), an optional `bias`, and the
+    cross entropy of kind "softmax" (linear logits, margin 0), "am" (AM-softmax / CosFace) or "aam" (AAM-softmax / ArcFace)
+    with `scale` and `margin` — the objective an x-vector extractor is trained with, for supervised adaptation of the
+    embeddings to a labelled set.  forward(z, labels) -> the loss (labels: integers, -1 = ignore the row); afterwards
+    `last_counts` (rows counted, of them classified right, labels out of range) and `last_pred` (argmax of the margin-free
+    logits) are device tensors of that call — nothing is read back."""
+
+    def __init__(self, num_classes, dim, kind="aam", scale=30.0, margin=0.2, bias=False):
+        super(SpeakerClassifier, self).__init__()
+        if kind not in ops.CLASSIFY_KINDS:
+            raise ValueError(f"kind is one of {sorted(ops.CLASSIFY_KINDS)}, got {kind!r}")
+        if kind == "softmax":
+            margin = 0.0
+        lin = nn.Linear(dim, num_classes, bias=bias)  # (the initialisation of nn.Linear)
+        self.weight = lin.weight
+        self.bias = lin.bias
+        self.kind, self.scale, self.margin = kind, float(scale), float(margin)
+        self.last_counts = self.last_pred = None
+
+    def forward(self, z, labels):
+        loss, self.last_counts, self.last_pred = _ClassifyLossFn.apply(
+            z, labels, (self.kind, self.scale, self.margin, torch.is_grad_enabled()), self.weight, self.bias)
+        return loss
+
+
 # ---------------------------------------------------------------------------------------------------
 # NeuralPlda
 # ---------------------------------------------------------------------------------------------------
@@ -553,6 +617,16 @@ class NeuralPlda(nn.Module):
         return _AllPairsLossFn.apply(z, speakers, groups, ops.LOSS_BCE, 0.0, [], opts, self.P_sqrt, self.Q,
                                      self.threshold_Xent)
 
+    def loss_classify(self, x, speakers, head):
+        """The classification loss of a SpeakerClassifier `head` on this model's embeddings:
+        head(self.extract_plda_embeddings(x), speakers).  x: (N, D0) x-vectors (for Etdnn_Xvec_NeuralPlda: whatever its
+        extract_plda_embeddings takes — each utterance is extracted, and back-propagated, once); `speakers`: one class index
+        per utterance (SpeakerBatchLoader's `spk`), -1 to ignore it."""
+        if self._reduce_flat is not None or self._reduce_sums is not None:
+            raise NotImplementedError("loss_classify on a data-parallel model: the head's gradients are not reduced "
+                                      "across ranks")
+        return head(self.extract_plda_embeddings(x), speakers)
+
     def identify(self, x_probe, gallery_or_xvectors, k=10):
         """1:N identification: (scores (R, k), indices (R, k)) of the k best-scoring gallery entries for every probe, best
         first (-1 / -inf where the gallery has fewer than k).  The gallery is a search.Gallery (embedded once, reusable) or
@@ -707,6 +781,9 @@ class DPlda(NeuralPlda):
 
     def loss_all_pairs(self, x, speakers, groups=None):
         raise NotImplementedError("loss_all_pairs covers the NeuralPlda score (P_sqrt, Q); DPlda has a quadratic-form head")
+
+    def loss_classify(self, x, speakers, head):
+        raise NotImplementedError("loss_classify works on the NeuralPlda embeddings; DPlda has a quadratic-form head")
 
     def identify(self, x_probe, gallery_or_xvectors, k=10):
         raise NotImplementedError("identify searches with the NeuralPlda score (P_sqrt, Q); DPlda has a quadratic-form head")

@@ -4,6 +4,7 @@ Every function takes torch tensors that live on a HIP device, enqueues the kerne
 current stream and returns torch tensors.  No CPU path exists: a CPU tensor is an error here
 (neuralplda_amd.models stages CPU inputs through the device, it never computes on the host).
 """
+import collections
 import ctypes
 import functools
 
@@ -585,6 +586,75 @@ def allpairs_loss(z, spk, P_sqrt, Q, thetas, betas, alpha, kind, grp=None, want_
             if t is not None:
                 t.zero_()
     return loss, dth, sums, (dzb[:, :D2] if want_grad else None), dP, dQ
+
+
+CLASSIFY_KINDS = {"softmax": 0, "am": 1, "aam": 2}  # the `kind` of nplda_classify_loss_f32
+
+ClassifyResult = collections.namedtuple("ClassifyResult", "loss counts rowloss pred dx dw db")
+
+
+def _rows16(t, D):
+    """`t` (n, D) as the kernels take a matrix: unit column stride, 16-byte aligned rows of a stride that is a multiple of 4."""
+    if t.shape[0] == 0 or (t.stride(1) == 1 and t.stride(0) >= D and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0):
+        return t
+    buf = torch.empty((t.shape[0], (D + 3) & ~3), dtype=torch.float32, device=t.device)  # columns >= D are never read
+    buf[:, :D] = t
+    return buf[:, :D]
+
+
+def classify_loss(x, labels, W, bias=None, kind="aam", scale=30.0, margin=0.2, want_dx=True, want_dw=True, class_chunks=0,
+                  row_chunks=0):
+    """nplda_classify_loss_f32: softmax ("softmax"), AM-softmax ("am") or AAM-softmax ("aam") cross entropy of the embeddings
+    x (N, D) against the class table W (C, D) with optional bias (C,) and integer labels (N,) (-1 = ignore the row)
+    -> ClassifyResult(loss 0-d, counts (3,) int64 = (rows counted, of them classified right, labels out of range),
+    rowloss (N,), pred (N,) int32 = argmax of the margin-free logits, dx (N, D) or None, dw (C, D) or None, db (C,) or None
+    (with want_dw, when there is a bias)).  The N x C logits are never materialised.  class_chunks / row_chunks: 0 = the
+    plan's choice."""
+    lib = _lib.load()
+    _require_dev_f32(x, "x")
+    _require_dev_f32(W, "W")
+    if kind not in CLASSIFY_KINDS:
+        raise ValueError(f"classify_loss: kind is one of {sorted(CLASSIFY_KINDS)}, got {kind!r}")
+    if x.dim() != 2 or W.dim() != 2 or x.shape[1] != W.shape[1]:
+        raise ValueError(f"x must be (N, D) and W (C, D), got {tuple(x.shape)} and {tuple(W.shape)}")
+    (N, D), C, dev = x.shape, W.shape[0], x.device
+    if bias is not None:
+        _require_dev_f32(bias, "bias")
+        if bias.shape != (C,):
+            raise ValueError(f"bias must be ({C},), got {tuple(bias.shape)}")
+        bias = bias.contiguous()
+    y = _labels(labels, "labels", N, dev)
+    x, W = _rows16(x, D), _rows16(W, D)
+    ld = (D + 3) & ~3
+    wsb = lib.nplda_classify_workspace_bytes(N, C, D, class_chunks, row_chunks)
+    if wsb == 0:
+        raise _lib.NpldaHipError(f"classify_loss: N = {N}, C = {C}, D = {D} is outside the compiled kernel set")
+    ws = torch.empty(wsb // 4, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+    rowloss = torch.empty(N, dtype=torch.float32, device=dev)
+    pred = torch.empty(N, dtype=torch.int32, device=dev)
+    dxb = torch.empty((N, ld), dtype=torch.float32, device=dev) if want_dx else None
+    dwb = torch.empty((C, ld), dtype=torch.float32, device=dev) if want_dw else None
+    db = torch.empty(C, dtype=torch.float32, device=dev) if want_dw and bias is not None else None
+    with _lib.on_device(dev):
+        code = lib.nplda_classify_loss_f32(_lib.ptr(x), x.stride(0) if N > 1 else ld, N, _lib.ptr(W),
+                                           W.stride(0) if C > 1 else ld, C, D, _lib.ptr(bias), _lib.ptr(y),
+                                           CLASSIFY_KINDS[kind], float(scale), float(margin), class_chunks, row_chunks,
+                                           _lib.ptr(loss), _lib.ptr(counts), _lib.ptr(rowloss), _lib.ptr(pred),
+                                           _lib.ptr(dxb), ld, _lib.ptr(dwb), ld, _lib.ptr(db), _lib.ptr(ws), wsb,
+                                           _lib.current_stream())
+    _lib.check(code, "nplda_classify_loss_f32")
+    if N == 0 or C == 0:  # the call is a no-op there: the formulas on an empty problem
+        loss.fill_(float("nan"))
+        counts.zero_()
+        rowloss.zero_()
+        pred.zero_()
+        for t in (dxb, dwb, db):
+            if t is not None:
+                t.zero_()
+    return ClassifyResult(loss, counts, rowloss, pred, None if dxb is None else dxb[:, :D],
+                          None if dwb is None else dwb[:, :D], db)
 
 
 def pack_params_into(packed, W1, b1, W2, b2, P_sqrt, Q):

@@ -550,7 +550,10 @@ class SpeakerBatchLoader:
 
     spk2utt: a Kaldi spk2utt path, a list of such paths, a dict {spk: [utt, ...]} or a list of (spk, [utt, ...]).
     groups: {spk: group} (speakers it does not name form one more group), or a list of spk2utt paths that are one group each
-    (spk2utt may then be None: their union).  device: yield torch tensors on it (rows int64, labels int32) instead of numpy."""
+    (spk2utt may then be None: their union).  device: yield torch tensors on it (rows int64, labels int32) instead of numpy.
+
+    The `spk` values index `loader.speakers` (0 .. `num_speakers` - 1, the same in every batch and epoch), so they are also
+    the class indices of a models.SpeakerClassifier(loader.num_speakers, dim) head for NeuralPlda.loss_classify."""
 
     def __init__(self, table, spk2utt, speakers_per_batch, utts_per_speaker, groups=None, seed=0, device=None):
         from . import backend
@@ -599,6 +602,11 @@ class SpeakerBatchLoader:
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
+
+    @property
+    def num_speakers(self):
+        """Number of speakers with an utterance in the table: `spk` labels lie in 0 .. num_speakers - 1."""
+        return len(self.speakers)
 
     def _chunks(self, rng):
         """Per speaker: this epoch's list of row chunks."""
