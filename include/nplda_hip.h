@@ -958,6 +958,40 @@ int nplda_xvec_backward_f32(const void* saved, size_t saved_bytes, const int64_t
                             int64_t total_frames, int pooling, const float* dxvec, int64_t lddx, const void* packed,
                             const void* packed_t, float* grad, void* ws, size_t ws_bytes, nplda_stream_t stream);
 
+/* The same extractor trained with batch-statistics batch norm (csrc/nplda_xvec_bn.hip, design/k27_xvec_batch_stats.md):
+ * XVectorNet_ETDNN_12Layer.extract under a plain model.train() (utils/models.py:90-93: unfold, Linear, ReLU, then
+ * nn.BatchNorm1d(affine=False) on the statistics of the batch).  For tdnn layer l the statistics run over V_l, the rows
+ * whose index inside their utterance is < T_u - ctx_l (ctx = 4, 4, 8, 8, 14, 14, 22, 22, 22, 22), over all utterances
+ * of the call: mu_l the mean, v_l the biased variance (fp64 sums in a fixed order), O_l = (ReLU(.) - mu_l) / sqrt(v_l + eps_l).
+ * These four calls mirror the four above.  Every utterance must be longer than 22 frames, and total_frames - 22 n_utts
+ * (the valid rows of tdnn7..tdnn10) must be 2 at least: otherwise NPLDA_EINVAL, and nothing is launched.
+ * Bytes of `saved`: what nplda_xvec_train_saved_bytes counts, plus mu_l and 1 / sqrt(v_l + eps_l) of every layer and the
+ * partial sums of the statistics. */
+size_t nplda_xvec_train_bn_saved_bytes(int64_t total_frames, int64_t n_utts);
+/* Bytes of the statistics table nplda_xvec_extract_train_bn_f32 fills: for l = 0..9 the batch mean (ld_l floats) then
+ * the UNBIASED batch variance v_l n_l / (n_l - 1) (ld_l floats), ld_l = 512 (tdnn10: 1504, the first 1500 used), then
+ * ten int64 n_l.  What torch's running_mean / running_var update takes. */
+size_t nplda_xvec_bn_stats_bytes(void);
+/* Where layer `layer` (0..9) keeps its ReLU-mask bytes inside `saved`: mask[row, col] (1 = the pre-activation was > 0
+ * and the row lies in V_l) is the byte at *offset + row * *row_stride + col.  For tests and tools. */
+int nplda_xvec_bn_mask_layout(int64_t total_frames, int64_t n_utts, int layer, size_t* offset, int64_t* row_stride);
+/* Arguments as nplda_xvec_extract_train_f32; the packed image's running statistics are not read.  eps: HOST array of
+ * ten floats (tdnn<i>.bn.eps).  stats: device table of nplda_xvec_bn_stats_bytes() bytes, 16-byte aligned. */
+int nplda_xvec_extract_train_bn_f32(const float* x, int layout, int64_t ld_in, const int64_t* offsets, int64_t n_utts,
+                                    int64_t total_frames, int pooling, const void* packed, const float* eps, float* out,
+                                    int64_t ldx, void* saved, size_t saved_bytes, void* stats, size_t stats_bytes,
+                                    nplda_stream_t stream);
+/* Workspace of one nplda_xvec_backward_bn_f32 call (that of nplda_xvec_backward_f32 plus the partial column sums). */
+size_t nplda_xvec_backward_bn_workspace_bytes(int64_t total_frames, int64_t n_utts);
+/* The autograd backward of the batch-statistics forward with respect to the 22 weights and biases, arguments as
+ * nplda_xvec_backward_f32.  With G_l = dL/dO_l, a_l = mean over V_l of G_l and c_l = mean over V_l of G_l O_l (fp64 sums
+ * in a fixed order, rows outside V_l excluded by their index, not by value): dL/dR_l = (G_l - a_l - O_l c_l) / sqrt(v_l +
+ * eps_l) on V_l, then the ReLU mask, then the data-gradient and weight-gradient kernels of the running-statistics path.
+ * grad is overwritten.  Deterministic, no atomics. */
+int nplda_xvec_backward_bn_f32(const void* saved, size_t saved_bytes, const int64_t* offsets, int64_t n_utts,
+                               int64_t total_frames, int pooling, const float* dxvec, int64_t lddx, const void* packed,
+                               const void* packed_t, float* grad, void* ws, size_t ws_bytes, nplda_stream_t stream);
+
 /* ---- feature front end of the extractor (Kaldi feature archives -> its input rows) ------------------------------ */
 
 /* csrc/nplda_feat.hip: what the x-vector recipe runs in front of nnet3-xvector-compute, `apply-cmvn-sliding

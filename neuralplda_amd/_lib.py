@@ -266,6 +266,15 @@ SIGNATURES = {
     "nplda_xvec_backward_workspace_bytes": (_c_sz, [_c_i64, _c_i64]),
     "nplda_xvec_backward_f32": (_c_int, [_c_vp, _c_sz, _c_vp, _c_i64, _c_i64, _c_int, _c_f32p, _c_i64, _c_vp, _c_vp,
                                          _c_f32p, _c_vp, _c_sz, _c_vp]),
+    "nplda_xvec_train_bn_saved_bytes": (_c_sz, [_c_i64, _c_i64]),
+    "nplda_xvec_bn_stats_bytes": (_c_sz, []),
+    "nplda_xvec_bn_mask_layout": (_c_int, [_c_i64, _c_i64, _c_int, ctypes.POINTER(_c_sz), ctypes.POINTER(_c_i64)]),
+    "nplda_xvec_extract_train_bn_f32": (_c_int, [_c_f32p, _c_int, _c_i64, _c_vp, _c_i64, _c_i64, _c_int, _c_vp,
+                                                 ctypes.POINTER(ctypes.c_float), _c_f32p, _c_i64, _c_vp, _c_sz, _c_vp,
+                                                 _c_sz, _c_vp]),
+    "nplda_xvec_backward_bn_workspace_bytes": (_c_sz, [_c_i64, _c_i64]),
+    "nplda_xvec_backward_bn_f32": (_c_int, [_c_vp, _c_sz, _c_vp, _c_i64, _c_i64, _c_int, _c_f32p, _c_i64, _c_vp, _c_vp,
+                                            _c_f32p, _c_vp, _c_sz, _c_vp]),
     "nplda_feat_decode_f32": (_c_int, [_c_vp, _c_sz, _c_vp, _c_vp, _c_i64, _c_i64, _c_f32p, _c_vp]),
     "nplda_feat_vad_energy_f32": (_c_int, [_c_f32p, _c_vp, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                            _c_int, _c_vp, _c_vp]),

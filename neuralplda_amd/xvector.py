@@ -24,6 +24,13 @@ utterance) held until backward, and the backward returns the gradients of the 22
 through HIP kernels (bn11, bn12, lin12 and finlin keep grad None, as in the reference).  The training path does not
 chunk a batch: one call per side.  There is no dL/dMFCC (an input that requires grad is an error).  The classifier path
 (`forward`, `prestatspool`, `postpooling`) is not provided.
+
+`XVectorNet_ETDNN_12Layer.enable_batch_stats()` opts in to batch-statistics batch norm (design/k27_xvec_batch_stats.md):
+with it on and all ten tdnn batch norms in training mode (a plain `model.train()`), `extract` / `extract_ragged`
+normalise every tdnn layer by the mean and biased variance of the call's own valid frames and update the running
+statistics as torch does (csrc/nplda_xvec_bn.hip), forward-only or, with `enable_backward()` under grad mode, through an
+autograd Function whose backward includes the batch-norm backward.  One call covers the whole batch.  With the switch
+off, or all ten in eval mode, everything above holds unchanged.
 """
 import ctypes
 import os
@@ -47,6 +54,7 @@ FEAT, XVEC_DIM, POOL_DIM = 30, 512, 1500
 LAYOUT_ROWS, LAYOUT_BCT = 0, 1  # include/nplda_hip.h NPLDA_XVEC_LAYOUT_*
 POOL_STD, POOL_VAR = 0, 1       # NPLDA_XVEC_POOL_*
 MAX_WORKSPACE_BYTES = 1 << 30   # per extraction call; larger batches are split by utterance
+MAX_BATCH_STATS_BYTES = 1 << 34  # `saved` of one batch-statistics call (about 31 KB per frame); larger batches raise
 
 
 def flops_per_frame():
@@ -162,6 +170,8 @@ class XVectorNet_ETDNN_12Layer(nn.Module):
     """utils/models.py:98-214: the 12-layer E-TDNN x-vector network.  `extract` / `extract_ragged` run on HIP."""
 
     backward_enabled = False  # class attribute: pickles written before the switch existed load with it off
+    batch_stats_enabled = False  # likewise
+    _bn_alloc = None  # tests: a callable (bytes, device, "saved" | "ws") -> uint8 tensor for the batch-statistics buffers
 
     def __init__(self, noclasses=13539, pooling_function=torch.std):
         super(XVectorNet_ETDNN_12Layer, self).__init__()
@@ -200,6 +210,13 @@ class XVectorNet_ETDNN_12Layer(nn.Module):
     def enable_backward(self, flag=True):
         """Opt in to backpropagation through `extract` / `extract_ragged` (a plain attribute, not state-dict content)."""
         self.backward_enabled = bool(flag)
+        return self
+
+    def enable_batch_stats(self, flag=True):
+        """Opt in to batch-statistics batch norm: with the switch on and all ten tdnn<i>.bn in training mode, `extract` /
+        `extract_ragged` normalise by the statistics of the call's frames and update the running statistics (a plain
+        attribute, not state-dict content).  With all ten in eval mode the switch changes nothing."""
+        self.batch_stats_enabled = bool(flag)
         return self
 
     def forward(self, x):
@@ -287,6 +304,59 @@ class XVectorNet_ETDNN_12Layer(nn.Module):
             raise RuntimeError("no backward through the x-vector extractor: its input must not require grad")
         return True
 
+    def _wants_batch_stats(self):
+        """True when the batch-statistics switch is on and all ten tdnn batch norms are in training mode; False when the
+        switch is off or all ten are in eval mode (the running-statistics paths, unchanged); raises for anything else."""
+        if not self.batch_stats_enabled:
+            return False
+        bns = [t.bn for t in self.tdnns()]
+        flags = [bool(bn.training) for bn in bns]
+        if not any(flags):
+            return False
+        if not all(flags):
+            on = [f"tdnn{i}" for i, f in enumerate(flags, 1) if f]
+            raise RuntimeError(f"mixed batch-norm modes: {', '.join(on)} in training mode and the rest in eval mode; "
+                               "batch statistics need all ten tdnn batch norms in training mode (model.train()), "
+                               "running statistics all ten in eval mode (.eval() or Etdnn_Xvec_NeuralPlda.train1())")
+        for i, bn in enumerate(bns, 1):
+            if bn.running_mean is None or bn.running_var is None:
+                raise RuntimeError(f"tdnn{i}.bn has no running statistics (track_running_stats=False): not implemented")
+            if bn.momentum is None:
+                raise RuntimeError(f"tdnn{i}.bn.momentum is None (cumulative moving average): not implemented, "
+                                   "set a momentum")
+        return True
+
+    def _check_batch_stats(self, x, lengths):
+        """The host-side checks of the batch-statistics path (before any device is touched) -> whether to record for
+        autograd."""
+        grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if grad and not self.backward_enabled:
+            raise RuntimeError("no backward through the x-vector extractor: freeze it with "
+                               "xvector_extractor.requires_grad_(False), extract under torch.no_grad() or call "
+                               "enable_backward()")
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise RuntimeError("no backward through the x-vector extractor: its input must not require grad")
+        U, R = len(lengths), int(sum(lengths))
+        if U > 0 and R - U * CONTEXT < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training: {U} utterance(s) of {R} frames leave "
+                             f"{R - U * CONTEXT} frame(s) after the context of {CONTEXT}")
+        return grad
+
+    def _extract_batch_stats(self, X, layout, lengths, dev, workspace_bytes, grad):
+        """The batch-statistics path of extract / extract_ragged: X on `dev`, float32 contiguous."""
+        U, R = len(lengths), int(sum(lengths))
+        if U == 0:
+            return torch.empty((0, XVEC_DIM), dtype=torch.float32, device=dev)
+        n = _lib.load().nplda_xvec_train_bn_saved_bytes(R, U)
+        limit = MAX_BATCH_STATS_BYTES if workspace_bytes is None else int(workspace_bytes)
+        if n > limit:
+            raise RuntimeError(f"batch-statistics extraction of {R} frames needs {n} bytes of saved activations, above "
+                               f"the limit of {limit} bytes; the statistics span the batch, so it is not split")
+        if grad:
+            return _ExtractBnFn.apply(self, X, layout, lengths, dev, *self._grad_params())
+        out, _ = _bn_forward(self, X, layout, lengths, dev)
+        return out
+
     # -- extraction ------------------------------------------------------------------------------
     def _run(self, x, layout, lengths, dev, workspace_bytes):
         """x on `dev`, float32 contiguous: (sum T, 30) for LAYOUT_ROWS, (U, 30, T) for LAYOUT_BCT."""
@@ -317,15 +387,20 @@ class XVectorNet_ETDNN_12Layer(nn.Module):
         on the HIP device (CPU input is staged through it and the result returned on the input's device)."""
         if x.dim() != 3 or x.shape[1] != FEAT:
             raise ValueError(f"extract expects (B, {FEAT}, T) features, got {tuple(x.shape)}")
-        grad = self._wants_backward(x)
-        if not grad:
+        bstats = self._wants_batch_stats()
+        grad = False if bstats else self._wants_backward(x)
+        if not (grad or bstats):
             self._check_mode(x)
         B, _, T = x.shape
         if B > 0 and T <= CONTEXT:
             raise ValueError(f"T = {T} frames is shorter than the extractor's context ({CONTEXT + 1} frames at least)")
+        if bstats:
+            grad = self._check_batch_stats(x, [T] * B)
         dev = _compute_device(x, self.lin11.weight)
         X = x.detach().to(dev, torch.float32).contiguous()
-        if grad:
+        if bstats:
+            out = self._extract_batch_stats(X, LAYOUT_BCT, [T] * B, dev, workspace_bytes, grad)
+        elif grad:
             out = _ExtractFn.apply(self, X, LAYOUT_BCT, [T] * B, dev, *self._grad_params())
         else:
             out = self._run(X, LAYOUT_BCT, [T] * B, dev, workspace_bytes)
@@ -343,12 +418,17 @@ class XVectorNet_ETDNN_12Layer(nn.Module):
         if short:
             raise ValueError(f"an utterance of {short[0]} frames is shorter than the extractor's context "
                              f"({CONTEXT + 1} frames at least; the reference's unfold raises)")
-        grad = self._wants_backward(frames)
-        if not grad:
+        bstats = self._wants_batch_stats()
+        grad = False if bstats else self._wants_backward(frames)
+        if not (grad or bstats):
             self._check_mode(frames)
+        if bstats:
+            grad = self._check_batch_stats(frames, lengths)
         dev = _compute_device(frames, self.lin11.weight)
         X = frames.detach().to(dev, torch.float32).contiguous()
-        if grad:
+        if bstats:
+            out = self._extract_batch_stats(X, LAYOUT_ROWS, lengths, dev, workspace_bytes, grad)
+        elif grad:
             out = _ExtractFn.apply(self, X, LAYOUT_ROWS, lengths, dev, *self._grad_params())
         else:
             out = self._run(X, LAYOUT_ROWS, lengths, dev, workspace_bytes)
@@ -556,6 +636,80 @@ class _ExtractFn(torch.autograd.Function):
                                                    d.data_ptr(), XVEC_DIM, packed.data_ptr(), packed_t.data_ptr(),
                                                    grad.data_ptr(), ws.data_ptr(), n, _lib.current_stream(dev)),
                        "nplda_xvec_backward_f32")
+        grads, o = [], 0
+        for sh in shapes:
+            k = int(np.prod(sh))
+            grads.append(grad[o:o + k].view(sh))
+            o += k
+        ctx.state = None
+        return (None,) * 5 + tuple(grads)
+
+
+def _bn_buffer(ext, n, dev, what):
+    return torch.empty(n, dtype=torch.uint8, device=dev) if ext._bn_alloc is None else ext._bn_alloc(n, dev, what)
+
+
+def _bn_forward(ext, X, layout, lengths, dev):
+    """One nplda_xvec_extract_train_bn_f32 call over the whole batch, then torch's running-statistics update on the
+    module's buffers (in-place torch ops, so that the packed-image cache, keyed on their versions, notices).
+    -> (x-vectors, state for _ExtractBnFn.backward)."""
+    U, R = len(lengths), int(sum(lengths))
+    kind = _pool_kind(ext.pooling_function)
+    packed = ext._packed(dev)
+    lib = _lib.load()
+    starts = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    out = torch.empty((U, XVEC_DIM), dtype=torch.float32, device=dev)
+    bns = [t.bn for t in ext.tdnns()]
+    with _lib.on_device(dev):
+        offs = torch.from_numpy(starts).to(dev)
+        n = lib.nplda_xvec_train_bn_saved_bytes(R, U)
+        saved = _bn_buffer(ext, n, dev, "saved")
+        ns = lib.nplda_xvec_bn_stats_bytes()
+        stats = torch.empty(ns, dtype=torch.uint8, device=dev)
+        eps = (ctypes.c_float * 10)(*[float(bn.eps) for bn in bns])
+        _lib.check(lib.nplda_xvec_extract_train_bn_f32(X.data_ptr(), layout, FEAT, offs.data_ptr(), U, R, kind,
+                                                       packed.data_ptr(), eps, out.data_ptr(), XVEC_DIM,
+                                                       saved.data_ptr(), n, stats.data_ptr(), ns,
+                                                       _lib.current_stream(dev)), "nplda_xvec_extract_train_bn_f32")
+        table = stats[:ns - 80].view(torch.float32)  # per layer mean | unbiased variance; ten int64 n_l follow
+    with torch.no_grad():
+        o = 0
+        for bn, (_, dout, _, _) in zip(bns, LAYERS):
+            ld = (dout + 15) // 16 * 16
+            m = float(bn.momentum)
+            mean, var = table[o:o + dout], table[o + ld:o + ld + dout]
+            bn.running_mean.mul_(1.0 - m).add_(mean.to(bn.running_mean.device, bn.running_mean.dtype), alpha=m)
+            bn.running_var.mul_(1.0 - m).add_(var.to(bn.running_var.device, bn.running_var.dtype), alpha=m)
+            if bn.num_batches_tracked is not None:
+                bn.num_batches_tracked.add_(1)
+            o += 2 * ld
+    return out, (saved, offs, packed, R, U, kind, dev)
+
+
+class _ExtractBnFn(torch.autograd.Function):
+    """extract / extract_ragged under batch-statistics batch norm, with a backward to the 22 tdnn1..tdnn10 / lin11
+    parameters (`_grad_params` order).  The saved buffer (~31 KB per frame) lives from forward to backward."""
+
+    @staticmethod
+    def forward(ctx, ext, X, layout, lengths, dev, *params):
+        packed_t = ext._packed_t(dev)  # (before the update of the running statistics drops the cache entry)
+        out, state = _bn_forward(ext, X, layout, lengths, dev)
+        ctx.state = state + (packed_t, ext, [tuple(p.shape) for p in params])
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        saved, offs, packed, R, U, kind, dev, packed_t, ext, shapes = ctx.state
+        lib = _lib.load()
+        with _lib.on_device(dev):
+            d = dout.detach().to(dev, torch.float32).contiguous()
+            grad = torch.empty(lib.nplda_xvec_grad_floats(), dtype=torch.float32, device=dev)
+            n = lib.nplda_xvec_backward_bn_workspace_bytes(R, U)
+            ws = _bn_buffer(ext, n, dev, "ws")
+            _lib.check(lib.nplda_xvec_backward_bn_f32(saved.data_ptr(), saved.numel(), offs.data_ptr(), U, R, kind,
+                                                      d.data_ptr(), XVEC_DIM, packed.data_ptr(), packed_t.data_ptr(),
+                                                      grad.data_ptr(), ws.data_ptr(), n, _lib.current_stream(dev)),
+                       "nplda_xvec_backward_bn_f32")
         grads, o = [], 0
         for sh in shapes:
             k = int(np.prod(sh))

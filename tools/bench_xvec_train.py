@@ -9,7 +9,14 @@ by backward of sum(x-vectors * G).  Reported: ms per forward + backward, frames/
 fraction of the fp32 MFMA peak (forward 2 K N per layer; backward the data gradients of tdnn2..tdnn10 and lin11 plus the
 weight gradients of all eleven layers).  The comparison is torch autograd on the same GPU over the reference's
 arithmetic (unfold + Linear per utterance, tests/xvec_grad_ref.py) for the training batch.  --profile-only runs the
-large case once (for `rocprofv3 --kernel-trace --stats -- python tools/bench_xvec_train.py --profile-only`)."""
+large case once (for `rocprofv3 --kernel-trace --stats -- python tools/bench_xvec_train.py --profile-only`).
+
+--batch-stats compares, in this process, the batch-statistics path (enable_batch_stats() under .train(),
+csrc/nplda_xvec_bn.hip) with the running-statistics path on the same two cases: forward + backward in alternating rounds,
+device events, medians; and sets the overhead against the time the added memory traffic would take at --stream-tbps
+(per frame, from the layer widths S = 9 x 2 KB + 6 KB: forward one statistics read and one read-modify-write, 3 S;
+backward the two-sum pass over G and O and the apply pass over G, O, the mask bytes and dA, 5.25 S).  With --profile-only
+it runs the large case once on the batch-statistics path."""
 import argparse
 import json
 import os
@@ -35,11 +42,13 @@ def flops(lengths):
     return fwd, bwd
 
 
-def make(dev):
+def make(dev, batch_stats=False):
     from neuralplda_amd import xvector
     from tests import xvec_ref
     m = xvector.XVectorNet_ETDNN_12Layer()
     xvec_ref.load_into(m, xvec_ref.make_params())
+    if batch_stats:
+        return m.to(dev).train().enable_backward().enable_batch_stats()
     return m.to(dev).eval().enable_backward()
 
 
@@ -63,6 +72,39 @@ def timed(fn, iters):
     return a.elapsed_time(b) / iters
 
 
+def added_traffic_bytes(frames):
+    S = sum(4 * ((dout + 15) // 16 * 16) for dout in [512] * 9 + [1500])
+    return (3 + 5.25) * S * frames
+
+
+def compare_batch_stats(m, mb, cases, dev, rounds, tbps):
+    """{case: medians of forward + backward on both paths, their ratio, and the overhead in units of the traffic time}."""
+    out = {}
+    for name, s, g in cases:
+        ms = {"running": [], "batch": []}
+        for model in (m, mb):  # warm-up: allocator, packed images
+            run_hip(model, s, g, dev)
+        torch.cuda.synchronize()
+        for _ in range(rounds):
+            for key, model in (("running", m), ("batch", mb)):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                run_hip(model, s, g, dev)
+                b.record()
+                torch.cuda.synchronize()
+                ms[key].append(a.elapsed_time(b))
+        frames = sum(sum(l) for _, l in s)
+        run_ms, bn_ms = float(np.median(ms["running"])), float(np.median(ms["batch"]))
+        traffic_ms = added_traffic_bytes(frames) / (tbps * 1e12) * 1e3
+        out[name] = {"frames": frames, "rounds": rounds, "ms_running_stats": round(run_ms, 3),
+                     "ms_batch_stats": round(bn_ms, 3), "ratio": round(bn_ms / run_ms, 3),
+                     "added_traffic_gb": round(added_traffic_bytes(frames) / 1e9, 2), "traffic_ms": round(traffic_ms, 3),
+                     "overhead_over_traffic": round((bn_ms - run_ms) / traffic_ms, 2),
+                     "ms_running_all": [round(v, 3) for v in ms["running"]],
+                     "ms_batch_all": [round(v, 3) for v in ms["batch"]]}
+    return out
+
+
 def case(rng, n, dev):
     lengths = [int(v) for v in rng.integers(200, 401, n)]
     frames = torch.from_numpy(rng.standard_normal((sum(lengths), 30)).astype(np.float32)).to(dev)
@@ -76,6 +118,8 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--json")
     ap.add_argument("--profile-only", action="store_true")
+    ap.add_argument("--batch-stats", action="store_true")
+    ap.add_argument("--stream-tbps", type=float, default=4.0)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(0)
@@ -83,12 +127,21 @@ def main():
     big = case(rng, a.big_utts, dev)
     Gbig = [torch.from_numpy(rng.standard_normal((a.big_utts, 512)).astype(np.float32)).to(dev)]
     if a.profile_only:
-        run_hip(m, [big], Gbig, dev)
+        run_hip(make(dev, True) if a.batch_stats else m, [big], Gbig, dev)
         torch.cuda.synchronize()
         return
     sides = [case(rng, a.pairs, dev) for _ in range(2)]
     G = [torch.from_numpy(rng.standard_normal((a.pairs, 512)).astype(np.float32)).to(dev) for _ in range(2)]
     out = {"gpu": torch.cuda.get_device_name(0), "iters": a.iters}
+    if a.batch_stats:
+        out.update(compare_batch_stats(m, make(dev, True), (("train_batch", sides, G), ("big", [big], Gbig)), dev,
+                                       a.iters, a.stream_tbps))
+        line = json.dumps(out)
+        print(line)
+        if a.json:
+            with open(a.json, "w") as f:
+                f.write(json.dumps(out, indent=1) + "\n")
+        return
     for name, s, g in (("train_batch", sides, G), ("big", [big], Gbig)):
         lengths = sum((l for _, l in s), [])
         ms = timed(lambda: run_hip(m, s, g, dev), a.iters)
