@@ -1293,6 +1293,92 @@ int nplda_spectral_kmeans_f64(const double* E, const int64_t* offsets_host, cons
                               int max_iters, int32_t* n_clusters, int32_t* n_iters, int32_t* labels, void* ws, size_t ws_bytes,
                               nplda_stream_t stream);
 
+/* ---- augmentation of 16-bit audio: reverberation and additive noise ------------------------------------------- */
+
+/* csrc/nplda_augment.hip, design/k28_augment.md: x -> x * h (uniformly partitioned overlap-save, block 256, transform 512,
+ * both transforms exact fp32 MFMA products against constant tables) -> + s noise -> gain -> float32 or int16.  A block's
+ * spectrum is 512 floats: [0, 256) the real parts of bins 0 .. 255, [256] the (real) Nyquist bin, [256 + k] the imaginary
+ * part of bin k = 1 .. 255.  The two tables are built by the caller (neuralplda_amd/augment.py) in float64, rounded once
+ * and laid out in MFMA fragment order, kb = 0 .. 31, w = 0 .. 3, lane = 0 .. 63, i = 0 .. 3:
+ *   forward [kb][w][u][lane][i], u < 8 = F(o = 16 (8 w + u) + (lane & 15), n = 16 kb + 4 (lane >> 4) + i):
+ *            F(o, n) = cos(2 pi o n / 512) for o < 256, (-1)^n for o = 256, -sin(2 pi (o - 256) n / 512) above
+ *   inverse [kb][w][u][lane][i], u < 4 = G(t = 16 (4 w + u) + (lane & 15), o = 16 kb + 4 (lane >> 4) + i), output
+ *            sample 256 + t of the inverse transform: G(t, 0) = 1 / 512, G(t, 256) = (-1)^t / 512,
+ *            G(t, o) = 2 cos(2 pi o (256 + t) / 512) / 512 for 0 < o < 256, -2 sin(2 pi (o - 256) (256 + t) / 512) / 512 above */
+#define NPLDA_AUGMENT_BLOCK 256       /* samples per block of the convolution (the transform has twice as many) */
+#define NPLDA_AUGMENT_TILE 32         /* blocks per thread block of the transform kernels */
+#define NPLDA_AUGMENT_GROUP 8         /* consecutive blocks of one utterance per thread block of the multiply-accumulate */
+#define NPLDA_AUGMENT_CHUNK 2048      /* samples per thread block of the element-wise kernels */
+#define NPLDA_AUGMENT_MAX_RIR 32768   /* taps: 128 partitions */
+
+typedef struct nplda_augment_utt {    /* one utterance of a call, 64 bytes */
+    int64_t in_off;                   /* its first sample in `samples` */
+    int64_t out_off;                  /* its first sample in `out` */
+    int64_t y_off;                    /* 256 times its first block: where x * h starts in the workspace (with a RIR) */
+    int32_t n, n_out;                 /* samples in, samples out */
+    int32_t shift;                    /* out[t] = (x * h)[shift + t]: the RIR's peak with shift_output, else 0 */
+    int32_t rir;                      /* index of the impulse response, -1: none */
+    int32_t ent_begin, ent_count;     /* its additive entries */
+    int32_t n_early;                  /* n + (b - a) - 1, the length of x * h[a:b] (with a RIR) */
+    int32_t normalize;                /* non-zero: gain sqrt(P_in / P_mix) unless volume > 0 */
+    float volume;                     /* > 0: the gain */
+    int32_t reserved;
+} nplda_augment_utt;
+
+typedef struct nplda_augment_entry {  /* one additive entry, 32 bytes */
+    int64_t noise_off;                /* the item's first sample in `noise` */
+    int32_t len, start, item, repeat; /* the item's length, the first output sample, the item, non-zero: periodic */
+    double ratio;                     /* 10^(-snr_db / 10), computed on the host */
+} nplda_augment_entry;
+
+typedef struct nplda_augment_call {   /* HOST struct; every pointer in it is a DEVICE pointer */
+    const int16_t* samples;
+    const nplda_augment_utt* utts;    /* n_utts */
+    const nplda_augment_entry* entries; /* n_entries */
+    const int64_t* in_off;            /* n_utts + 1 sample offsets */
+    const int32_t* in_len;            /* n_utts */
+    const int32_t* in_chunk_off;      /* n_utts + 1: cumulative ceil(n / CHUNK) */
+    const int32_t* out_chunk_off;     /* n_utts + 1: cumulative ceil(n_out / CHUNK) */
+    const int32_t* blk_off;           /* n_utts + 1: cumulative ceil((n + L - 1) / BLOCK), 0 blocks without a RIR */
+    const int32_t* grp_off;           /* n_utts + 1: cumulative ceil(blocks / GROUP) */
+    const int32_t* rir_of;            /* n_utts: nplda_augment_utt.rir */
+    const int32_t* early_len;         /* n_utts: nplda_augment_utt.n_early */
+    const float* rir_spectra;         /* nplda_augment_spectra_f32 of every RIR and of its early window */
+    const int32_t* rir_parts;         /* per RIR: first partition, partitions, the early window's first, its partitions */
+    const int16_t* noise;
+    const int64_t* noise_sums;        /* per noise item: nplda_augment_power_i64 */
+    const void* forward_table;        /* 1 MiB, 16-byte aligned */
+    const void* inverse_table;        /* 512 KiB, 16-byte aligned */
+    void* out;                        /* float32 or int16, sum of n_out */
+    int32_t* clipped;                 /* n_utts: saturated samples (int16 output; zeroed otherwise) */
+    int64_t n_utts, n_entries, total_blocks, total_groups, total_in_chunks, total_out_chunks;
+    int64_t max_conv_len;             /* the largest n + L - 1 of the call */
+    int32_t max_rir_len;              /* the largest L in use */
+    int32_t out_i16;                  /* non-zero: int16 by round-half-to-even with saturation */
+} nplda_augment_call;
+
+/* Bytes of table `which` (0 forward, 1 inverse), 0 otherwise. */
+size_t nplda_augment_table_bytes(int which);
+/* spectra[b] (512 floats each) = the forward transform of partition b of every filter: filter f is src_len[f] >= 1 floats at
+ * src + src_off[f] and takes blocks blk_off[f] .. blk_off[f + 1] = blk_off[f] + ceil(src_len[f] / 256) (DEVICE arrays; the
+ * caller gives the smallest and the largest length from the host).  min_len < 1: NPLDA_EINVAL; max_len >
+ * NPLDA_AUGMENT_MAX_RIR: NPLDA_EUNSUPPORTED, before any launch. */
+int nplda_augment_spectra_f32(const float* src, const int64_t* src_off, const int32_t* src_len, const int32_t* blk_off,
+                              int64_t n_filters, int64_t total_blocks, int32_t min_len, int32_t max_len,
+                              const void* forward_table, float* spectra, nplda_stream_t stream);
+/* sums[i] = the exact sum of squares of item i (samples[item_off[i]] .. samples[item_off[i + 1]]), chunk_off its cumulative
+ * ceil(length / NPLDA_AUGMENT_CHUNK); all DEVICE arrays.  Integer atomics only: the same value on every call. */
+int nplda_augment_power_i64(const int16_t* samples, const int64_t* item_off, const int32_t* chunk_off, int64_t n_items,
+                            int64_t total_chunks, int64_t* sums, nplda_stream_t stream);
+/* Host arithmetic: the workspace of a call (20 bytes per sample of x * h, 8 per block and per output chunk, 16 per utterance, 4 per entry). */
+size_t nplda_augment_workspace_bytes(int64_t n_utts, int64_t n_entries, int64_t total_blocks, int64_t total_out_chunks);
+/* One augmentation call (design/k28_augment.md gives the arithmetic).  The launch count depends on the struct's counts only
+ * (no transform launches when total_blocks == 0), nothing is read back, and the call can be captured in a graph.
+ * NPLDA_EUNSUPPORTED before any launch: max_rir_len > NPLDA_AUGMENT_MAX_RIR, or max_conv_len / the block and chunk counts
+ * beyond the int32 indexing.  NPLDA_ENOSPC: ws_bytes below nplda_augment_workspace_bytes.  n_utts == 0 is a no-op.  No
+ * floating-point atomics: same bits on every call, and an utterance's result does not depend on the batch. */
+int nplda_augment_batch(const nplda_augment_call* call, void* ws, size_t ws_bytes, nplda_stream_t stream);
+
 /* ---- measurement utility ------------------------------------------------------------------------------------- */
 
 /* Shader-clock probe for bench.py (no reference counterpart): one wave that stays resident for window_us microseconds

@@ -284,6 +284,12 @@ SIGNATURES = {
     "nplda_mfcc_image_bytes": (_c_sz, [_c_vp, _c_int]),
     "nplda_mfcc_frames_f32": (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_f32p, _c_vp, _c_vp, _c_vp, _c_f32p,
                                        _c_vp]),
+    "nplda_augment_table_bytes": (_c_sz, [_c_int]),
+    "nplda_augment_spectra_f32": (_c_int, [_c_f32p, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, ctypes.c_int32, ctypes.c_int32, _c_vp,
+                                           _c_f32p, _c_vp]),
+    "nplda_augment_power_i64": (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp]),
+    "nplda_augment_workspace_bytes": (_c_sz, [_c_i64] * 4),
+    "nplda_augment_batch": (_c_int, [_c_vp, _c_vp, _c_sz, _c_vp]),
     "nplda_class_scatter_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_int]),
     "nplda_class_scatter_f32": (_c_int, [_c_f32p, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp, _c_i64, _c_int, _c_f32p, _c_vp, _c_vp,
                                          _c_vp, _c_int, _c_vp, _c_sz, _c_vp]),

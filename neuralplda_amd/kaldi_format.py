@@ -27,7 +27,7 @@ __all__ = ["read_vector", "read_matrix", "read_plda", "plda_psi_to_pq", "read_ve
            "read_scp", "load_vector_ark", "load_vector_scp", "write_vector_ark", "fold_init",
            "write_matrix_binary", "write_vector_binary", "write_plda_binary", "read_feature_ark", "read_feature_scp",
            "load_feature_scp", "FeatureArchive", "FEAT_DESC", "FEAT_FORMATS", "KaldiFormatError", "read_wav",
-           "load_wav_scp", "write_feature_ark", "fold_arrays"]
+           "load_wav_scp", "write_wav", "write_feature_ark", "fold_arrays"]
 
 
 class KaldiFormatError(ValueError):
@@ -643,6 +643,20 @@ def read_wav(f, channel=0):
     buf = np.memmap(path, dtype=np.uint8, mode="r")
     rate, ch, body, frames = _wav_layout(buf, off or 0, path)
     return rate, np.array(_wav_channel(buf, body, frames, ch, channel, path), dtype=np.int16)
+
+
+def write_wav(path, samples, sample_frequency):
+    """A 16-bit mono RIFF/WAVE file (format tag 1, a 44-byte header) that read_wav reads back; samples: int16."""
+    x = np.asarray(samples)
+    if x.dtype != np.int16 or x.ndim != 1:
+        raise ValueError("write_wav: expected a one-dimensional int16 array")
+    rate, nbytes = int(sample_frequency), 2 * int(x.shape[0])
+    if rate < 1 or nbytes + 36 > 0xFFFFFFFF:
+        raise ValueError(f"write_wav: sample rate {rate}, {nbytes} bytes of samples")
+    with open(path, "wb") as fh:
+        fh.write(b"RIFF" + struct.pack("<I", 36 + nbytes) + b"WAVEfmt " + struct.pack("<IHHIIHH", 16, 1, 1, rate, 2 * rate, 2, 16) +
+                 b"data" + struct.pack("<I", nbytes))
+        fh.write(x.astype("<i2").tobytes())
 
 
 def load_wav_scp(path, entries=None, sample_frequency=None, channel=0):
