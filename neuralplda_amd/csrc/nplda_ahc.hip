@@ -14,6 +14,7 @@
 #include <cmath>
 
 #include "nplda_cohort_common.h"
+#include "nplda_ragged.h"
 
 namespace {
 
@@ -24,11 +25,21 @@ constexpr int kAhcBlock = 1024;     // threads of the clustering block
 constexpr int kAhcWaves = kAhcBlock / 64;
 constexpr int kAhcMaxN = 16384;     // 8 n^2 bytes of fp64 numerators per problem: 2 GiB
 constexpr long long kMaxP = (1ll << 22) - 1;  // a grid of P blocks of 1024 threads stays below 2^32 threads
-constexpr int kNone = 0x7fffffff;   // "no partner"
 constexpr int kBlockScanRows = 8;   // a merge of a problem above kSmallN rows with up to this many rows to scan again has
 constexpr int kSmallN = 2048;       // the whole block scan each; any other merge gives every such row to one wave
 
-// ---- host: the ragged layout ------------------------------------------------------------------------------------------------
+// ---- the ragged layout (csrc/nplda_ragged.h) ------------------------------------------------------------------------------------
+
+// what a problem of n rows takes: n^2 matrix elements, max(n - 1, 0) merge records, and in the workspace n^2 fp64 numerators
+// with five words per row (cache value 8, partner, size, rep, todo 4 each)
+enum { kElems, kRecords, kWsBytes, kTerms };
+struct AhcTerms {
+    __host__ __device__ void operator()(long long n, long long, long long* t) const {
+        t[kElems] = n * n;
+        t[kRecords] = n > 1 ? n - 1 : 0;
+        t[kWsBytes] = 8 * n * n + 24 * n;
+    }
+};
 
 struct RaggedPlan {
     int status;
@@ -38,31 +49,19 @@ struct RaggedPlan {
 
 RaggedPlan ragged_plan(const int64_t* offs, int64_t P) {
     RaggedPlan r = {NPLDA_OK, 0, 0, 0, 0, 0};
-    if (P < 0 || (P > 0 && !offs)) {
-        r.status = NPLDA_EINVAL;
-        return r;
-    }
-    if (P > kMaxP) {
-        r.status = NPLDA_EUNSUPPORTED;
-        return r;
-    }
-    if (P > 0 && offs[0] != 0) r.status = NPLDA_EINVAL;
-    size_t ws = 0;
-    for (int64_t p = 0; p < P && r.status == NPLDA_OK; ++p) {
-        const long long n = offs[p + 1] - offs[p];
-        if (n < 0) {
-            r.status = NPLDA_EINVAL;
-        } else if (n > kAhcMaxN) {
-            r.status = NPLDA_EUNSUPPORTED;
-        } else {
-            if (n > r.max_n) r.max_n = n;
-            r.elems += n * n;
-            r.records += n > 1 ? n - 1 : 0;
-            ws += (size_t)(8 * n * n + 24 * n);
-        }
-    }
+    long long ws = 0;
+    r.status = ragged_walk(offs, offs, P, kMaxP, [&](long long n, long long) {
+        if (n > kAhcMaxN) return NPLDA_EUNSUPPORTED;
+        long long t[kTerms];
+        AhcTerms()(n, n, t);
+        if (n > r.max_n) r.max_n = n;
+        r.elems += t[kElems];
+        r.records += t[kRecords];
+        ws += t[kWsBytes];
+        return NPLDA_OK;
+    });
     if (r.status == NPLDA_OK && P > 0) r.rows = offs[P];
-    r.ws_bytes = up256(ws) + 256;
+    r.ws_bytes = up256((size_t)ws) + 256;
     return r;
 }
 
@@ -80,35 +79,13 @@ struct Starts {
     long long row0, n, elem0, rec0, ws0;  // first table row, rows, first matrix element, first merge record, workspace byte
 };
 
-// Integer sums over the problems in front of p, by the whole block (any block size that is a multiple of 64, at most 1024).
 __device__ __forceinline__ Starts problem_starts(const long long* __restrict__ offs, long long p, long long* red /* [3 * 16] */) {
-    long long e = 0, r = 0, w = 0;
-    for (long long q = threadIdx.x; q < p; q += blockDim.x) {
-        const long long n = offs[q + 1] - offs[q];
-        e += n * n;
-        r += n > 1 ? n - 1 : 0;
-        w += 8 * n * n + 24 * n;
-    }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        e += __shfl_xor(e, s, 64);
-        r += __shfl_xor(r, s, 64);
-        w += __shfl_xor(w, s, 64);
-    }
-    const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[wave] = e;
-        red[16 + wave] = r;
-        red[32 + wave] = w;
-    }
-    __syncthreads();
+    long long sum[kTerms];
+    ragged_starts(offs, p, AhcTerms(), red, sum);
     Starts s;
-    s.elem0 = s.rec0 = s.ws0 = 0;
-    for (int v = 0; v < nw; ++v) {
-        s.elem0 += red[v];
-        s.rec0 += red[16 + v];
-        s.ws0 += red[32 + v];
-    }
+    s.elem0 = sum[kElems];
+    s.rec0 = sum[kRecords];
+    s.ws0 = sum[kWsBytes];
     s.row0 = offs[p];
     s.n = offs[p + 1] - s.row0;
     return s;
@@ -252,25 +229,6 @@ struct AhcArgs {
 // exactly, a correctly rounded quotient), the numerator itself otherwise
 __device__ __forceinline__ double link_value(int linkage, double num, int sa, int sb) {
     return linkage == 0 ? num / (double)((long long)sa * (long long)sb) : num;
-}
-
-// (v1, j1) before (v2, j2): the larger value, the lower index among equal ones; kNone loses to everything
-__device__ __forceinline__ bool before(double v1, int j1, double v2, int j2) {
-    if (j1 == kNone) return false;
-    if (j2 == kNone) return true;
-    return v1 > v2 || (v1 == v2 && j1 < j2);
-}
-
-__device__ __forceinline__ void wave_best(double& v, int& j) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        const double ov = __shfl_xor(v, s, 64);
-        const int oj = __shfl_xor(j, s, 64);
-        if (before(ov, oj, v, j)) {
-            v = ov;
-            j = oj;
-        }
-    }
 }
 
 // The best (value, index) over the whole block, with a payload x that travels with the winner; the same result on every

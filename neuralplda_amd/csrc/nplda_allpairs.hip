@@ -51,12 +51,6 @@ WsLayout ws_layout(int64_t N, int Dp) {
     return L;
 }
 
-__device__ __forceinline__ long long wave_sum_ll(long long v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // ---- N_t, N_n from the labels alone: block b counts the trials (i, j > i) of its 256 rows i ---------------------------------
 __global__ __launch_bounds__(kCountTile) void ap_count(const int* __restrict__ spk, const int* __restrict__ grp, int N,
                                                        long long* __restrict__ cnt) {
@@ -81,7 +75,7 @@ __global__ __launch_bounds__(kCountTile) void ap_count(const int* __restrict__ s
             }
         }
     }
-    const long long wt = wave_sum_ll(nt), wa = wave_sum_ll(nall);
+    const long long wt = wave_sum(nt), wa = wave_sum(nall);
     if ((threadIdx.x & 63) == 0) {
         red[threadIdx.x >> 6][0] = wt;
         red[threadIdx.x >> 6][1] = wa - wt;
@@ -153,8 +147,8 @@ __global__ __launch_bounds__(256, 2) void ap_main(const float* __restrict__ Zp, 
         ct_l += cnt[2 * b];
         cn_l += cnt[2 * b + 1];
     }
-    ct_l = wave_sum_ll(ct_l);
-    cn_l = wave_sum_ll(cn_l);
+    ct_l = wave_sum(ct_l);
+    cn_l = wave_sum(cn_l);
     if (lane == 0) {
         cred[wave][0] = ct_l;
         cred[wave][1] = cn_l;
@@ -296,7 +290,7 @@ __global__ __launch_bounds__(256, 2) void ap_main(const float* __restrict__ Zp, 
     }
 #pragma unroll
     for (int n = 0; n < NS; ++n) {
-        const double v = wave_sum_d(acc[n]);
+        const double v = wave_sum(acc[n]);
         if (lane == 0) red[wave][n] = v;
     }
     __syncthreads();

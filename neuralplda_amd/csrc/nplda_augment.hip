@@ -50,12 +50,6 @@ __device__ inline int item_of(const int32_t* __restrict__ off, int I, int r) {
     return lo;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {  // xor butterfly: the same pairs at every level on every call
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // ---- the two transforms ------------------------------------------------------------------------------------------------------
 
 enum { SIGNAL = 0, FILTER = 1, SYNTH = 2, SYNTH_POWER = 3 };
@@ -314,8 +308,7 @@ __global__ __launch_bounds__(NT) void aug_power_kernel(const int16_t* __restrict
             acc += (unsigned long long)(v * v);
         }
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+    acc = wave_sum(acc);
     if ((tid & 63) == 0) ws[tid >> 6] = acc;
     __syncthreads();
     if (tid == 0) atomicAdd(sums + it, ws[0] + ws[1] + ws[2] + ws[3]);  // integers: any order, the same sum
@@ -409,7 +402,7 @@ __global__ __launch_bounds__(NT) void aug_mix_sum_kernel(const MixArgs a) {
             }
         }
     }
-    acc = wave_sum_f64(acc);
+    acc = wave_sum(acc);  // (the xor butterfly: the same pairs at every level on every call)
     if ((tid & 63) == 0) ws[tid >> 6] = acc;
     __syncthreads();
     if (tid == 0) a.mpart[c] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
@@ -440,8 +433,7 @@ __global__ __launch_bounds__(NT) void aug_store_kernel(const MixArgs a) {
         }
     }
     if (I16) {
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) nclip += __shfl_xor(nclip, m, 64);
+        nclip = wave_sum(nclip);
         if ((tid & 63) == 0 && nclip) atomicAdd(a.clipped + u, nclip);  // integers
     }
 }

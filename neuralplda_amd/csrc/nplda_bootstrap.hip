@@ -362,10 +362,8 @@ __global__ __launch_bounds__(64) void finish_kernel(const FinishArgs f) {
             if (code == CODE_TGT) t0 += (double)cw;
             if (code == CODE_NON) n0 += (double)cw;
         }
-        for (int off = 32; off > 0; off >>= 1) {  // integers: exact in any order
-            t0 += __shfl_xor(t0, off);
-            n0 += __shfl_xor(n0, off);
-        }
+        t0 = wave_sum(t0);  // integers: exact in any order
+        n0 = wave_sum(n0);
         const size_t cs = (size_t)a.nchunks * kTile, cq = (size_t)(rq / kChunkRuns) * kTile + l;
         t0 += a.part[0 * qs + rq * kTile + l] + a.ctot[0 * cs + cq];
         n0 += a.part[1 * qs + rq * kTile + l] + a.ctot[1 * cs + cq];

@@ -56,9 +56,7 @@ __device__ __forceinline__ void block_reduce_store(double (&v)[NQ], double* __re
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
-        double x = v[q];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+        const double x = wave_sum(v[q]);
         if (lane == 0) red[wave][q] = x;
     }
     __syncthreads();
@@ -74,8 +72,7 @@ __device__ __forceinline__ void reduce_partials(const double* __restrict__ part,
     for (int q = wave; q < nq; q += kBlock / 64) {
         double x = 0.0;
         for (int j = lane; j < nblocks; j += 64) x += part[(size_t)j * kPartStride + q];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+        x = wave_sum(x);
         if (lane == 0) sh[q] = x;
     }
     __syncthreads();
@@ -89,11 +86,8 @@ __global__ __launch_bounds__(kBlock) void count_kernel(const float* __restrict__
         ct += l == 1;
         cn += l == 0;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        ct += __shfl_xor(ct, off, 64);
-        cn += __shfl_xor(cn, off, 64);
-    }
+    ct = wave_sum(ct);
+    cn = wave_sum(cn);
     if ((threadIdx.x & 63) == 0) {
         if (ct) atomicAdd(&st->nt, (unsigned long long)ct);
         if (cn) atomicAdd(&st->nn, (unsigned long long)cn);

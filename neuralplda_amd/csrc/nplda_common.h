@@ -107,6 +107,51 @@ __device__ __forceinline__ float wave_xor_add(float v, int mask) {
     return v + __shfl_xor(v, mask, 64);
 }
 
+// Sum (minimum) over the 64 lanes of a wave, every lane getting the result: the xor butterfly, masks 32, 16 .. 1 — the same
+// pairs at every level on every call, so a floating-point sum has one fixed order.  Instantiated for float, double, int,
+// unsigned, long long and unsigned long long.
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+// ... over the lanes 0 .. n2 - 1 (n2 a power of two, wave-uniform), on each of those lanes: masks n2 / 2 .. 1
+template <class T>
+__device__ __forceinline__ T wave_sum(T v, int n2) {
+    for (int m = n2 >> 1; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+template <class T>
+__device__ __forceinline__ T wave_min(T v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const T w = __shfl_xor(v, m, 64);
+        v = w < v ? w : v;
+    }
+    return v;
+}
+
+// The best (value, index) of a wave, on every lane.  (v1, j1) before (v2, j2): the larger value, the lower index among equal
+// ones; kNone ("no candidate") loses to everything.
+constexpr int kNone = 0x7fffffff;
+__device__ __forceinline__ bool before(double v1, int j1, double v2, int j2) {
+    if (j1 == kNone) return false;
+    if (j2 == kNone) return true;
+    return v1 > v2 || (v1 == v2 && j1 < j2);
+}
+__device__ __forceinline__ void wave_best(double& v, int& j) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const double ov = __shfl_xor(v, m, 64);
+        const int oj = __shfl_xor(j, m, 64);
+        if (before(ov, oj, v, j)) {
+            v = ov;
+            j = oj;
+        }
+    }
+}
+
 // Sum over the 16 lanes of a DPP row, every lane of the row getting the result: the four steps of the xor butterfly
 // (masks 1, 2, 4, 8 — the same pairs of partial sums at every level, hence the same bits: fp add commutes) as quad_perm /
 // row_half_mirror / row_mirror operand modifiers instead of four ds_bpermute round trips.

@@ -156,19 +156,6 @@ __device__ __forceinline__ void add_run(int* C, unsigned long long R, unsigned l
     }
 }
 
-__device__ __forceinline__ long long wave_min_ll(long long v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const long long w = __shfl_xor(v, o, 64);
-        v = w < v ? w : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ long long wave_sum_ll(long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // Maximum-weight one-to-one assignment on the n x n corner of C (n <= 64, weights >= 0), on ONE wave with all 64 lanes active:
 // shortest augmenting paths on the costs -C with integer potentials.  Lane j holds column j (its potential v, the row p assigned
 // to it, the slack minv and the predecessor column `way` of the current search) and, as a row, the potential u of row j and
@@ -176,7 +163,7 @@ __device__ __forceinline__ long long wave_sum_ll(long long v) {
 // taken: that is the whole tie rule, and it makes the mapping a function of C alone.  -> rowcol of this lane's row (every row
 // below n has a column afterwards).
 __device__ int assign_rows(const int* C, int n, int lane) {
-    const long long kInf = 0x1fffffffffffffffll, kNone = 0x7fffffffffffffffll;
+    const long long kInf = 0x1fffffffffffffffll, kClosed = 0x7fffffffffffffffll;
     long long u = 0, v = 0;
     int p = -1, rowcol = -1;
     for (int i = 0; i < n; ++i) {
@@ -194,9 +181,9 @@ __device__ int assign_rows(const int* C, int n, int lane) {
                     way = j0;
                 }
             }
-            const long long cand = open ? minv : kNone;
-            const long long delta = wave_min_ll(cand);
-            if (delta == kNone) break;  // (no open column: cannot happen while i < n)
+            const long long cand = open ? minv : kClosed;
+            const long long delta = wave_min(cand);
+            if (delta == kClosed) break;  // (no open column: cannot happen while i < n)
             const int j1 = __builtin_ctzll(__ballot(cand == delta));
             const bool in_tree = lane == i || (rowcol >= 0 && ((usedmask >> rowcol) & 1ull));
             if (in_tree) u += delta;
@@ -316,7 +303,7 @@ __global__ __launch_bounds__(kDerBlock) void der_count_kernel(DerArgs a) {
         const int col = assign_rows(sh.C, n, lane);
         const int w = (lane < n && col >= 0) ? sh.C[lane * kDerMaxS + col] : 0;
         a.map_ref[prob * kDerMaxS + lane] = w > 0 ? col : -1;  // a pair that shares no scored frame is no mapping
-        const long long matched = wave_sum_ll(w);
+        const long long matched = wave_sum((long long)w);
         if (lane < kNCounts) a.counts[prob * kNCounts + lane] = lane < 5 ? (long long)sh.red[lane] : matched;
     }
 }

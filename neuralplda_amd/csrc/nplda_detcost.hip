@@ -44,10 +44,8 @@ __device__ __forceinline__ long long label_fixed(float v) {
 
 // block sum of a pair of 64-bit integers, returned in every thread
 __device__ __forceinline__ void block_sum2(long long& q1, long long& q0, long long (*red)[2]) {
-    for (int off = 32; off > 0; off >>= 1) {
-        q1 += __shfl_xor(q1, off);
-        q0 += __shfl_xor(q0, off);
-    }
+    q1 = wave_sum(q1);
+    q0 = wave_sum(q0);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) { red[wave][0] = q1; red[wave][1] = q0; }
     __syncthreads();

@@ -92,12 +92,9 @@ __global__ __launch_bounds__(64) void gb_v_kernel(const float* __restrict__ mut,
             wt += lt * (double)mut[c];
         }
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        acc += __shfl_xor(acc, m, 64);
-        wn += __shfl_xor(wn, m, 64);
-        wt += __shfl_xor(wt, m, 64);
-    }
+    acc = wave_sum(acc);
+    wn = wave_sum(wn);
+    wt = wave_sum(wt);
     if (threadIdx.x == 0) {
         out[L.ov + i] = f < D1 ? (float)acc : 0.f;
         cpart[i] = f < D1 ? (double)mun[r] * wn - (double)mut[r] * wt : 0.0;
@@ -109,8 +106,7 @@ __global__ __launch_bounds__(64) void gb_c_kernel(GbLayout L, float* __restrict_
     const int n = 2 * L.NB * 16;
     double c = 0.0;
     for (int i = threadIdx.x; i < n; i += 64) c += cpart[i];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
+    c = wave_sum(c);
     __syncthreads();
     for (int i = threadIdx.x; i < n; i += 64) cpart[i] = 0.0;  // leave the slack as zeros
     if (threadIdx.x == 0) out[L.oc] = (float)c;

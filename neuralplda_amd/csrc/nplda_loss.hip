@@ -27,7 +27,7 @@ __device__ __forceinline__ void block_reduce_add(double (&acc)[NS], double* out,
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
-        const double v = wave_sum_d(acc[i]);
+        const double v = wave_sum(acc[i]);
         if (lane == 0) red[wave][i] = v;
     }
     __syncthreads();

@@ -10,12 +10,6 @@ namespace nplda_loss {
 constexpr int kThreads = 256;
 constexpr long long kSingleBlockMax = 4096;
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // One block over a whole (16-byte aligned) batch: float4 groups, four groups per thread loaded as one batch with clamped
 // indices (a scalar one-load-per-iteration loop is waited out load by load), then the < 4 tail elements.
 template <class F>
@@ -49,7 +43,7 @@ __device__ __forceinline__ void block_totals(double (&acc)[NS], double* tot, dou
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
-        const double v = wave_sum_d(acc[i]);
+        const double v = wave_sum(acc[i]);
         if (lane == 0) red[wave][i] = v;
     }
     __syncthreads();

@@ -258,8 +258,7 @@ __global__ __launch_bounds__(256) void normalize_bwd_paired_kernel(const float* 
     const float* y = paired + k * ldp + h * D1;
     float dot = 0.f;
     for (int f = lane; f < D1; f += 64) dot = fmaf(y[f], dy[f], dot);
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) dot += __shfl_xor(dot, m, 64);
+    dot = wave_sum(dot);
     const float r = rn[w];
     if (r >= 1e12f) dot = 0.f;
     for (int f = lane; f < ldz; f += 64) du[w * ldz + f] = f < D1 ? (dy[f] - y[f] * dot) * r : 0.f;

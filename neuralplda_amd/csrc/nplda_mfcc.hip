@@ -65,12 +65,6 @@ __device__ inline int utt_of(const int64_t* __restrict__ offsets, int U, int64_t
     return lo;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {  // xor butterfly: the same pairs at every level on every call
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // NBW: 16-bin blocks per wave (P / 128), MB: 16-blocks of the mel bins and of the cepstra (2: B <= 32, 4: B <= 64)
 template <int NBW, int MB>
 __global__ __launch_bounds__(NT, 2) void mfcc_kernel(const MfccArgs a) {
@@ -122,8 +116,7 @@ __global__ __launch_bounds__(NT, 2) void mfcc_kernel(const MfccArgs a) {
             isum += s;
             v[t] = (float)s;
         }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) isum += __shfl_xor(isum, m, 64);  // |sum| <= 512 * 32768: exact
+        isum = wave_sum(isum);  // |sum| <= 512 * 32768: exact
         const float mean = a.remove_dc ? (float)isum / (float)N : 0.f;
         float e = 0.f;
 #pragma unroll

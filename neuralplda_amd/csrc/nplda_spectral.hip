@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "nplda_cohort_common.h"
+#include "nplda_ragged.h"
 
 // nothing in this file may be contracted into a multiply-add: the mirrored pieces of the Jacobi pass and the k-means sums
 // are specified one multiplication and one addition at a time
@@ -44,6 +45,19 @@ __host__ __device__ inline long long cell_bytes(long long n) {
 __host__ __device__ inline long long prob_bytes(long long n) { return (8 * n + 15) & ~15ll; }
 __host__ __device__ inline long long vec_rows(long long n, int maxc) { return n < maxc + 1 ? n : maxc + 1; }
 
+// what a problem of n rows takes with C candidates (csrc/nplda_ragged.h): n^2 matrix elements, the workspace bytes of its C
+// cells and its k-means distances, and the rows x n doubles of its cells in `vectors`.  kVecs is a start on the device only:
+// the caller sizes `vectors` (ops.spectral), and make_plan, which has no maxc, leaves that term unread.
+enum { kElems, kWsBytes, kVecs, kTerms };
+struct Terms {
+    int C, maxc;
+    __host__ __device__ void operator()(long long n, long long, long long* t) const {
+        t[kElems] = n * n;
+        t[kWsBytes] = C * cell_bytes(n) + prob_bytes(n);
+        t[kVecs] = C * vec_rows(n, maxc) * n;
+    }
+};
+
 struct Plan {
     int status;
     long long rows, max_n, elems;
@@ -52,30 +66,22 @@ struct Plan {
 
 Plan make_plan(const int64_t* offs, int64_t P, int C) {
     Plan r = {NPLDA_OK, 0, 0, 0, 0};
-    if (P < 0 || (P > 0 && !offs) || C < 0 || C > kMaxC) {
+    if (C < 0 || C > kMaxC) {
         r.status = NPLDA_EINVAL;
         return r;
     }
-    if (P > kMaxP) {
-        r.status = NPLDA_EUNSUPPORTED;
-        return r;
-    }
-    if (P > 0 && offs[0] != 0) r.status = NPLDA_EINVAL;
-    size_t ws = 0;
-    for (int64_t p = 0; p < P && r.status == NPLDA_OK; ++p) {
-        const long long n = offs[p + 1] - offs[p];
-        if (n < 0) {
-            r.status = NPLDA_EINVAL;
-        } else if (n > kMaxN) {
-            r.status = NPLDA_EUNSUPPORTED;
-        } else {
-            if (n > r.max_n) r.max_n = n;
-            r.elems += n * n;
-            ws += (size_t)(C * cell_bytes(n) + prob_bytes(n));
-        }
-    }
+    long long ws = 0;
+    r.status = ragged_walk(offs, offs, P, kMaxP, [&](long long n, long long) {
+        if (n > kMaxN) return NPLDA_EUNSUPPORTED;
+        long long t[kTerms];
+        Terms{C, 0}(n, n, t);
+        if (n > r.max_n) r.max_n = n;
+        r.elems += t[kElems];
+        ws += t[kWsBytes];
+        return NPLDA_OK;
+    });
     if (r.status == NPLDA_OK && P > 0) r.rows = offs[P];
-    r.ws_bytes = up256(ws) + 256;
+    r.ws_bytes = up256((size_t)ws) + 256;
     return r;
 }
 
@@ -85,36 +91,14 @@ struct Starts {
     long long row0, n, elem0, ws0, vec0;
 };
 
-// Integer sums over the problems in front of p, by the whole block (a multiple of 64 threads, at most 1024).
 __device__ __forceinline__ Starts problem_starts(const long long* __restrict__ offs, long long p, int C, int maxc,
                                                  long long* red /* [48] */) {
-    long long e = 0, w = 0, v = 0;
-    for (long long q = threadIdx.x; q < p; q += blockDim.x) {
-        const long long n = offs[q + 1] - offs[q];
-        e += n * n;
-        w += C * cell_bytes(n) + prob_bytes(n);
-        v += C * vec_rows(n, maxc) * n;
-    }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        e += __shfl_xor(e, s, 64);
-        w += __shfl_xor(w, s, 64);
-        v += __shfl_xor(v, s, 64);
-    }
-    const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[wave] = e;
-        red[16 + wave] = w;
-        red[32 + wave] = v;
-    }
-    __syncthreads();
+    long long sum[kTerms];
+    ragged_starts(offs, p, Terms{C, maxc}, red, sum);
     Starts s;
-    s.elem0 = s.ws0 = s.vec0 = 0;
-    for (int u = 0; u < nw; ++u) {
-        s.elem0 += red[u];
-        s.ws0 += red[16 + u];
-        s.vec0 += red[32 + u];
-    }
+    s.elem0 = sum[kElems];
+    s.ws0 = sum[kWsBytes];
+    s.vec0 = sum[kVecs];
     s.row0 = offs[p];
     s.n = offs[p + 1] - s.row0;
     return s;
@@ -209,8 +193,7 @@ __global__ __launch_bounds__(kGraphBlock) void graph_kernel(const Args a) {
             if (j != i) A[(size_t)i * ne + j] = v;
             W[(size_t)i * ne + j] = j == i ? 1.0 : 0.0;
         }
-#pragma unroll
-        for (int sft = 32; sft > 0; sft >>= 1) d += __shfl_xor(d, sft, 64);
+        d = wave_sum(d);
         if (lane == 0) {
             A[(size_t)i * ne + i] = d;  // (the pad row of an odd n: 0)
             if (a.degrees && i < n) a.degrees[s.row0 * a.C + (long long)cand * n + i] = d;
@@ -271,8 +254,7 @@ __global__ __launch_bounds__(BLK) void jacobi_kernel(const Args a) {
         const double v = A[e];
         ss += v * v;
     }
-#pragma unroll
-    for (int sft = 32; sft > 0; sft >>= 1) ss += __shfl_xor(ss, sft, 64);
+    ss = wave_sum(ss);
     if (lane == 0) wred[wave] = ss;
     __syncthreads();
     ss = 0.0;
@@ -379,25 +361,17 @@ __global__ __launch_bounds__(BLK) void jacobi_kernel(const Args a) {
         const int k = lane + 1;
         const bool valid = k >= kfloor && k <= K;
         double gap = 0.0;
-        int bk = 0x7fffffff;
+        int bk = kNone;
         if (valid) {
             gap = dg[at(k)] - dg[at(k - 1)];
             bk = k;
         }
-#pragma unroll
-        for (int sft = 32; sft > 0; sft >>= 1) {
-            const double og = __shfl_xor(gap, sft, 64);
-            const int ok = __shfl_xor(bk, sft, 64);
-            if (ok != 0x7fffffff && (bk == 0x7fffffff || og > gap || (og == gap && ok < bk))) {
-                gap = og;
-                bk = ok;
-            }
-        }
+        wave_best(gap, bk);
         if (lane == 0) {
             const double top = dg[at(n - 1)];
             int ks = kfloor < (n > 1 ? n : 1) ? kfloor : (n > 1 ? n : 1);
             double ratio = __builtin_inf();
-            if (n > 1 && bk != 0x7fffffff && top > 0.0) {
+            if (n > 1 && bk != kNone && top > 0.0) {
                 const double g = gap / top;
                 if (g > 0.0) {
                     ks = bk;
@@ -417,8 +391,7 @@ __global__ __launch_bounds__(BLK) void jacobi_kernel(const Args a) {
         const double* w = W + (size_t)at(r) * ne;
         double s2 = 0.0;
         for (int j = lane; j < n; j += 64) s2 += w[j] * w[j];
-#pragma unroll
-        for (int sft = 32; sft > 0; sft >>= 1) s2 += __shfl_xor(s2, sft, 64);
+        s2 = wave_sum(s2);
         const double len = sqrt(s2);
         for (int j = lane; j < n; j += 64) {
             const double v = w[j] / len;
@@ -458,23 +431,15 @@ __device__ void kmeans_block(KmShared& sh, const double* __restrict__ X, long lo
     for (int i = tid; i < n; i += B) mind[i] = dist2(X, rs, cs, i, sh.cen, d);
     for (int c = 1; c < k; ++c) {
         double v = -1.0;
-        int bi = 0x7fffffff;
+        int bi = kNone;
         for (int i = tid; i < n; i += B) {  // rows ascending on a thread: the first of equal values stays
             const double m = mind[i];
-            if (bi == 0x7fffffff || m > v) {
+            if (bi == kNone || m > v) {
                 v = m;
                 bi = i;
             }
         }
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) {
-            const double ov = __shfl_xor(v, s, 64);
-            const int oi = __shfl_xor(bi, s, 64);
-            if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > v || (ov == v && oi < bi))) {
-                v = ov;
-                bi = oi;
-            }
-        }
+        wave_best(v, bi);
         if (lane == 0) {
             sh.bv[wave] = v;
             sh.bi[wave] = bi;
@@ -483,7 +448,7 @@ __device__ void kmeans_block(KmShared& sh, const double* __restrict__ X, long lo
         v = sh.bv[0];
         bi = sh.bi[0];
         for (int w = 1; w < B / 64; ++w)
-            if (sh.bi[w] != 0x7fffffff && (bi == 0x7fffffff || sh.bv[w] > v || (sh.bv[w] == v && sh.bi[w] < bi))) {
+            if (before(sh.bv[w], sh.bi[w], v, bi)) {
                 v = sh.bv[w];
                 bi = sh.bi[w];
             }

@@ -9,7 +9,7 @@
 // __syncthreads() only: no cross-block hand-off, no atomics, no memset, nothing read back; every sum has one fixed order.
 #include <cmath>
 
-#include "nplda_common.h"
+#include "nplda_ragged.h"
 
 namespace {
 
@@ -50,6 +50,16 @@ __host__ __device__ inline Slice slice_of(long long T, long long S, long long D)
     return s;
 }
 
+// what a problem of T rows and S speaker slots takes (csrc/nplda_ragged.h): T S posteriors and its slice of the workspace
+enum { kGamma, kWsDoubles, kTerms };
+struct VbTerms {
+    long long D;
+    __host__ __device__ void operator()(long long T, long long S, long long* t) const {
+        t[kGamma] = T * S;
+        t[kWsDoubles] = slice_of(T, S, D).total;
+    }
+};
+
 // ---- host: the ragged layout ---------------------------------------------------------------------------------------------------
 
 struct VbPlan {
@@ -64,24 +74,24 @@ VbPlan vb_plan(const int64_t* offs, const int64_t* spk, int64_t P, int D2) {
         r.status = NPLDA_EINVAL;
         return r;
     }
-    if (P > kMaxP || D2 > NPLDA_MAX_DIM) {
+    if (D2 > NPLDA_MAX_DIM) {  // (after the invalid arguments, before the tables' contents: where the walk has P > kMaxP)
         r.status = NPLDA_EUNSUPPORTED;
         return r;
     }
-    if (P > 0 && (offs[0] != 0 || spk[0] != 0)) r.status = NPLDA_EINVAL;
     long long ws = 0;
     int unsupported = 0;
-    for (int64_t p = 0; p < P && r.status == NPLDA_OK; ++p) {
-        const long long T = offs[p + 1] - offs[p], S = spk[p + 1] - spk[p];
-        if (T < 0 || S < 0 || (S == 0 && T > 0)) {
-            r.status = NPLDA_EINVAL;
-        } else if (T > kVbMaxT || S > kVbMaxS) {
+    r.status = ragged_walk(offs, spk, P, kMaxP, [&](long long T, long long S) {
+        if (S == 0 && T > 0) return NPLDA_EINVAL;
+        if (T > kVbMaxT || S > kVbMaxS) {
             unsupported = 1;  // (an invalid problem further on still wins)
-        } else {
-            r.gamma_elems += T * S;
-            ws += slice_of(T, S, D2).total;
+            return NPLDA_OK;
         }
-    }
+        long long t[kTerms];
+        VbTerms{D2}(T, S, t);
+        r.gamma_elems += t[kGamma];
+        ws += t[kWsDoubles];
+        return NPLDA_OK;
+    });
     if (r.status == NPLDA_OK && unsupported) r.status = NPLDA_EUNSUPPORTED;
     if (r.status == NPLDA_OK && P > 0) {
         r.rows = offs[P];
@@ -123,16 +133,10 @@ __device__ __forceinline__ long long uniform(long long v) {
     return (long long)(((unsigned long long)hi << 32) | lo);
 }
 
-// the sum of v over the lanes 0 .. n2 - 1 of a wave (n2 a power of two), on each of those lanes: a butterfly, one fixed order
-__device__ __forceinline__ double wave_sum(double v, int n2) {
-    for (int o = n2 >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // the sum of v over the block, the same bits on every thread: lanes by butterfly, then the waves in order.  ONE barrier:
 // consecutive calls alternate between two sets of slots, so the slots a call writes were last read two calls ago.
 __device__ __forceinline__ double block_sum(VbShared& sh, int& slot, double v) {
-    v = wave_sum(v, 64);
+    v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) sh.sum[slot][threadIdx.x >> 6] = v;
     __syncthreads();
     double t = sh.sum[slot][0];
@@ -149,17 +153,16 @@ __global__ __launch_bounds__(kVbBlock) void vbhmm_kernel(const VbArgs a) {
     const int D = a.D;
 
     // where this problem's rows, speaker slots, posteriors and workspace slice start: integer sums over the problems before it
+    // (two tables and this kernel's eight slots per term: nplda_ragged.h's ragged_starts takes one table and sixteen)
     long long ge = 0, we = 0;
     for (long long q = tid; q < prob; q += kVbBlock) {
-        const long long Tq = a.offs[q + 1] - a.offs[q], Sq = a.spk[q + 1] - a.spk[q];
-        ge += Tq * Sq;
-        we += slice_of(Tq, Sq, D).total;
+        long long t[kTerms];
+        VbTerms{D}(a.offs[q + 1] - a.offs[q], a.spk[q + 1] - a.spk[q], t);
+        ge += t[kGamma];
+        we += t[kWsDoubles];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        ge += __shfl_xor(ge, o, 64);
-        we += __shfl_xor(we, o, 64);
-    }
+    ge = wave_sum(ge);
+    we = wave_sum(we);
     if (lane == 0) {
         sh.red[wave] = ge;
         sh.red[kVbWaves + wave] = we;
@@ -245,7 +248,7 @@ __global__ __launch_bounds__(kVbBlock) void vbhmm_kernel(const VbArgs a) {
         for (int s = wave; s < S; s += kVbWaves) {
             double n0 = 0.0;
             for (int t = lane; t < T; t += 64) n0 += gamma[(long long)t * S + s];
-            n0 = wave_sum(n0, 64);
+            n0 = wave_sum(n0);
             if (lane == 0) sh.N[s] = n0;
         }
         __syncthreads();
@@ -315,8 +318,8 @@ __global__ __launch_bounds__(kVbBlock) void vbhmm_kernel(const VbArgs a) {
                 k0 += ksd[(long long)s * D + d];
                 e0 += esd[(long long)s * D + d];
             }
-            k0 = wave_sum(k0, 64);
-            e0 = wave_sum(e0, 64);
+            k0 = wave_sum(k0);
+            e0 = wave_sum(e0);
             if (lane == 0) {
                 sh.K[s] = 0.5 * k0;
                 sh.E[s] = e0;
@@ -464,13 +467,13 @@ __global__ __launch_bounds__(kVbBlock) void vbhmm_kernel(const VbArgs a) {
         for (int s = wave; s < S; s += kVbWaves) {
             double e0 = 0.0;
             for (int t = 1 + lane; t < T; t += 64) e0 = fma(pe[(long long)t * S + s] * bw[(long long)t * S + s], wt[t], e0);
-            e0 = wave_sum(e0, 64);
+            e0 = wave_sum(e0);
             if (lane == 0) sh.pinew[s] = gamma[s] + enter * sh.pi[s] * e0;
         }
         __syncthreads();
         // (every wave: the same butterfly over the same LDS words, so the same bits on every thread; a tree, because the
         // rounding of `tot` is an error common to every pi_s)
-        const double tot = wave_sum(lane < S ? sh.pinew[lane] : 0.0, 64), esum = wave_sum(lane < S ? sh.E[lane] : 0.0, 64);
+        const double tot = wave_sum(lane < S ? sh.pinew[lane] : 0.0), esum = wave_sum(lane < S ? sh.E[lane] : 0.0);
         const double el = Lev + 0.5 * Fb * esum;
         __syncthreads();  // everyone has read pinew and E; pi may change
         if (tid < S) sh.pi[tid] = sh.pinew[tid] / tot;

@@ -224,6 +224,37 @@ def test_float_sizes_around_small_n(linkage):
         check([ar.int_matrix(N0 + 1, 5)], linkage, "exact above small_n")
 
 
+def test_batch_past_the_block_equals_the_single_runs_bit_for_bit():
+    """P = 1100 problems against the 1024 threads of ahc_kernel (and the 256 of score_matrix_kernel): where a problem's
+    regions start is a sum over the problems in front of it, and from problem `block` on a thread of that sum adds more than
+    one term.  Fifteen distinct tiny problems in turn (0, 1, 2, 3, 5 rows) and one of 70 rows last, whose starts depend on
+    every term: every problem's outputs equal, bit for bit, those of a call of its own on the same data."""
+    from neuralplda_amd import _lib, ops
+    P = 1100
+    assert P - 1 > _lib.load().nplda_ahc_block()
+    sizes = [(0, 1, 2, 3, 5)[i % 5] for i in range(15)] + [70]
+    pick = [p % 15 for p in range(P - 1)] + [15]
+    offs = np.concatenate([[0], np.cumsum([sizes[i] for i in pick])]).astype(np.int64)
+    # the score matrix of a table whose rows repeat with the problems
+    roff = np.concatenate([[0], np.cumsum(sizes)])
+    z, q, P_sqrt, Q = table(150, int(roff[-1]), 7)
+    packed = packed_for(P_sqrt, Q)
+    rows = np.concatenate([np.arange(roff[i], roff[i + 1]) for i in pick])
+    got = blocks(ops.score_matrix(_dev(z[rows]), _dev(q[rows]), packed, offs).cpu().numpy(), offs)
+    alone = [ops.score_matrix(_dev(z[roff[i]:roff[i + 1]]), _dev(q[roff[i]:roff[i + 1]]), packed).cpu().numpy() if n else
+             np.zeros((0, 0), np.float32) for i, n in enumerate(sizes)]
+    for p, i in enumerate(pick):
+        assert np.array_equal(bits(got[p]), bits(alone[i])), ("score_matrix", p)
+    # the clustering, on exact matrices
+    mats = [ar.int_matrix(n, 100 + i) for i, n in enumerate(sizes)]
+    rec, nm, nc, lab = run_ahc([mats[i] for i in pick], "average")
+    ro = np.concatenate([[0], np.cumsum([max(sizes[i] - 1, 0) for i in pick])])
+    singles = [run_ahc([m], "average") for m in mats]
+    assert singles[15][1][0] == 69
+    for p, i in enumerate(pick):
+        assert_same((rec[ro[p]:ro[p + 1]], nm[p:p + 1], nc[p:p + 1], lab[offs[p]:offs[p + 1]]), singles[i], ("ahc", p))
+
+
 # ---- 3. end to end ------------------------------------------------------------------------------------------------------------------------
 
 class NC:

@@ -184,6 +184,54 @@ def test_kmeans_ragged_k_equals_n_and_empty_centres():
     assert ncl[3] == 64
 
 
+# ---- 4b. a batch with more problems than a block has threads -----------------------------------------------------------------------------
+
+def per_problem(res, offs):
+    """Every output of ops.spectral (embedding, degrees and vectors included) on the host, split by problem."""
+    host = lambda t: t.cpu().numpy()  # noqa: E731
+    ev, ks, ratio, sw, cv = host(res.eigenvalues), host(res.kstar), host(res.ratio), host(res.n_sweeps), host(res.converged)
+    chosen, ncl, it, lab = host(res.chosen), host(res.n_clusters), host(res.n_kmeans_iters), host(res.labels)
+    emb, deg, vec = host(res.embedding).reshape(-1), host(res.degrees), host(res.vectors)
+    n, C, mc = np.diff(offs), len(res.neighbours), res.max_clusters
+    voff = np.concatenate([[0], np.cumsum(C * np.minimum(mc + 1, n) * n)])
+    out = []
+    for p in range(n.size):
+        r0, k = int(offs[p]), min(int(ks[p, chosen[p]]), int(n[p]))
+        out.append((ev[p], ks[p], ratio[p], sw[p], cv[p], chosen[p:p + 1], ncl[p:p + 1], it[p:p + 1], lab[r0:r0 + n[p]],
+                    emb[r0 * mc:r0 * mc + n[p] * k], deg[r0 * C:(r0 + n[p]) * C], vec[voff[p]:voff[p + 1]]))
+    return out
+
+
+def test_batch_past_the_block_equals_the_single_runs_bit_for_bit():
+    """P = 300 problems against blocks of 256 threads (graph, small eigensolver, finish, k-means): where a problem's matrix,
+    workspace and vectors start is a sum over the problems in front of it, and from problem 256 on a thread of that sum adds
+    more than one term.  Fifteen distinct tiny problems in turn (0, 1, 2, 3, 5 rows) and one of 20 rows last, whose starts
+    depend on every term: every problem's outputs equal, bit for bit, those of a call of its own on the same data."""
+    from neuralplda_amd import ops
+    P, cands = 300, (1, 4, 200)
+    sizes = [(0, 1, 2, 3, 5)[i % 5] for i in range(15)] + [20]
+    pick = [p % 15 for p in range(P - 1)] + [15]
+    kw = dict(return_embedding=True, return_degrees=True, return_vectors=True)
+    mats = [sr.planted(n, 2 if n >= 4 else 1, 3.0, 300 + i)[0] for i, n in enumerate(sizes)]
+    res, offs = run([mats[i] for i in pick], cands, **kw)
+    got = per_problem(res, offs)
+    singles = [per_problem(*run([m], cands, **kw))[0] for m in mats]
+    assert singles[15][6][0] >= 2 and singles[15][4].all()                        # the last problem: clusters, every cell converged
+    for p, i in enumerate(pick):
+        assert len(got[p]) == len(singles[i]) == 12
+        for f, (a, b) in enumerate(zip(got[p], singles[i])):
+            assert np.array_equal(bits(a), bits(b)), (p, f)
+    # ops.spectral_kmeans on rows that repeat with the problems
+    rng = np.random.default_rng(23)
+    E = [rng.standard_normal((n, 3)) for n in sizes]
+    rows = np.concatenate([[0], np.cumsum([sizes[i] for i in pick])]).astype(np.int64)
+    lab, ncl, it = (t.cpu().numpy() for t in ops.spectral_kmeans(_dev(np.concatenate([E[i] for i in pick])), rows, 4))
+    alone = [[t.cpu().numpy() for t in ops.spectral_kmeans(_dev(e), [0, e.shape[0]], 4)] for e in E]
+    assert alone[15][1][0] == 4
+    for p, i in enumerate(pick):
+        assert np.array_equal(lab[rows[p]:rows[p + 1]], alone[i][0]) and ncl[p] == alone[i][1][0] and it[p] == alone[i][2][0], p
+
+
 # ---- 5. end to end ----------------------------------------------------------------------------------------------------------------------------
 
 class NC:

@@ -181,6 +181,43 @@ def test_ragged_batch_equals_the_single_runs_bit_for_bit():
         assert np.array_equal(bits(a), bits(b))
 
 
+def test_batch_past_the_block_equals_the_single_runs_bit_for_bit():
+    """P = 600 problems against the 512 threads of the workgroup: where a problem's posteriors and workspace slice start is a
+    sum over the problems in front of it, and from problem 512 on a thread of that sum adds more than one term.  Fifteen
+    distinct tiny problems in turn (0, 1, 2, 3, 5 rows) and one of 40 rows and 3 speakers last, whose starts depend on every
+    term: every problem's outputs equal, bit for bit, those of a call of its own on the same data."""
+    from neuralplda_amd import _lib, ops
+    P, D2 = 600, 150
+    assert P - 1 > _lib.load().nplda_vbhmm_block()
+    Ts = [(0, 1, 2, 3, 5)[i % 5] for i in range(15)] + [40]
+    Ss = [0, 1, 2, 3, 2, 2, 1, 1, 2, 3, 1, 1, 2, 1, 4, 3]     # empty problems with and without speaker slots
+    rng = np.random.default_rng(10)
+    probs = [vr.make_problem(60 + i, T, max(S, 1), D2, 1.0) for i, (T, S) in enumerate(zip(Ts, Ss))]
+    psi = probs[0][1]
+    pis = [rng.dirichlet(np.ones(S)) if S else np.zeros(0) for S in Ss]
+    pick = [p % 15 for p in range(P - 1)] + [15]
+    offs = np.concatenate([[0], np.cumsum([Ts[i] for i in pick])])
+    spk = np.concatenate([[0], np.cumsum([Ss[i] for i in pick])])
+    goff = np.concatenate([[0], np.cumsum([Ts[i] * Ss[i] for i in pick])])
+    kw = dict(epsilon=1e-3, max_iters=12)
+    out = ops.vbhmm(_dev(padded(np.concatenate([probs[i][0] for i in pick]))), offs, spk, _dev(psi),
+                    labels_init=_dev(np.concatenate([probs[i][2] for i in pick])),
+                    pi_init=_dev(np.concatenate([pis[i] for i in pick])), **kw)
+    gamma, pi, elbo, n_iters, labels, n_spk = (t.cpu().numpy() for t in out)
+    singles = [run_one(probs[i][0], psi, Ss[i], labels_init=_dev(probs[i][2]), pi_init=_dev(pis[i]), **kw) if Ts[i] else None
+               for i in range(16)]
+    assert 1 <= singles[15].n_iters <= 12 and np.isfinite(singles[15].gamma).all()
+    for p, i in enumerate(pick):
+        one = singles[i]
+        if one is None:
+            assert n_iters[p] == 0 and n_spk[p] == 0 and np.isnan(elbo[p]).all(), p
+            continue
+        assert np.array_equal(bits(gamma[goff[p]:goff[p + 1]]), bits(one.gamma.ravel())), p
+        assert np.array_equal(bits(pi[spk[p]:spk[p + 1]]), bits(one.pi)) and np.array_equal(bits(elbo[p]), bits(one.elbo)), p
+        assert n_iters[p] == one.n_iters and n_spk[p] == one.n_speakers, p
+        assert np.array_equal(labels[offs[p]:offs[p + 1]], one.labels), p
+
+
 # ---- 4. the initialisers -------------------------------------------------------------------------------------------------------------
 
 def test_initialisers():
