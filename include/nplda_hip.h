@@ -1379,6 +1379,68 @@ size_t nplda_augment_workspace_bytes(int64_t n_utts, int64_t n_entries, int64_t 
  * floating-point atomics: same bits on every call, and an utterance's result does not depend on the batch. */
 int nplda_augment_batch(const nplda_augment_call* call, void* ws, size_t ws_bytes, nplda_stream_t stream);
 
+/* ---- resampling and speed perturbation of 16-bit audio ---------------------------------------------------------- */
+
+/* csrc/nplda_resample.hip, design/k29_resample.md: a rational-ratio polyphase windowed-sinc resampler over a ragged batch.
+ * With g = gcd(rin, rout), iu = rin / g, ou = rout / g, an utterance of n samples gives m = ceil(n ou / iu) samples
+ *   y[k] = gain * sum_{t < taps} w[t][k mod ou] * x[(k div ou) iu + first[k mod ou] + t],   x = 0 outside [0, n),
+ * one chain of float32 fused multiply-adds per output in increasing t, times gain in float32, stored as float32 or as int16
+ * by round-half-to-even with saturation.  The caller (neuralplda_amd/resample.py) builds first[] and w[] in float64 from the
+ * integer tick distance i ou - k iu and rounds the weights once; a phase with fewer weights is padded with zeros at its end,
+ * and `taps` is padded with zero weights to a multiple of 4 (a ratio whose taps is not is skipped); first[] must not
+ * decrease with the phase and first[ou - 1] <= first[0] + iu. */
+#define NPLDA_RESAMPLE_CHUNK 1024         /* output samples per thread block */
+#define NPLDA_RESAMPLE_MAX_UNITS 1024     /* iu and ou */
+#define NPLDA_RESAMPLE_MAX_TAPS 128
+#define NPLDA_RESAMPLE_MAX_LDS_BYTES 65536 /* of a chunk's input span as float32 */
+
+typedef struct nplda_resample_utt {   /* one utterance of a call, 32 bytes */
+    int64_t in_off;                   /* its first sample in `samples` */
+    int64_t out_off;                  /* its first sample in `out` */
+    int32_t n, m;                     /* samples in, samples out (m == n for a copy) */
+    int32_t ratio;                    /* its row of `ratios`, -1: a copy times the gain, no filter */
+    float gain;
+} nplda_resample_utt;
+
+typedef struct nplda_resample_ratio { /* one ratio of a call, 32 bytes */
+    int32_t iu, ou, taps, reserved;
+    int64_t first_off;                /* its ou first-input offsets in `first` */
+    int64_t weight_off;               /* its taps x ou weights in `weights`, [tap][phase] */
+} nplda_resample_ratio;
+
+typedef struct nplda_resample_call {  /* HOST struct; every pointer in it is a DEVICE pointer */
+    const int16_t* samples;           /* 16-byte aligned */
+    const nplda_resample_utt* utts;   /* n_utts */
+    const nplda_resample_ratio* ratios; /* n_ratios */
+    const int32_t* first;
+    const float* weights;
+    const int32_t* chunks;            /* total_chunks x 2: nplda_resample_chunk_table */
+    void* out;                        /* float32 or int16, sum of m */
+    int32_t* clipped;                 /* n_utts: the samples that saturated (set to zero by the call first) */
+    int64_t n_utts, n_ratios, total_chunks;
+    int32_t max_iu, max_ou, max_taps; /* the largest of `ratios`, from the host */
+    int32_t max_span;                 /* the largest nplda_resample_span_floats of `ratios` */
+    int32_t out_i16;                  /* non-zero: int16 */
+    int32_t reserved;
+} nplda_resample_call;
+
+/* NPLDA_RESAMPLE_CHUNK. */
+int nplda_resample_chunk(void);
+/* Host arithmetic: the float32 slots of LDS a chunk of this ratio stages, 0 for a ratio beyond the limits. */
+size_t nplda_resample_span_floats(int32_t iu, int32_t ou, int32_t taps);
+/* Host arithmetic on HOST arrays: out_off holds n_utts + 1 non-decreasing output offsets starting at 0; returns the number
+ * of chunks (ceil(m / NPLDA_RESAMPLE_CHUNK) per utterance) and, if table != NULL, writes (utterance, chunk of the utterance)
+ * per chunk, in order.  A negative status instead: NPLDA_EINVAL for a malformed table, NPLDA_EUNSUPPORTED beyond the int32
+ * indexing, NPLDA_ENOSPC if `capacity` chunks do not hold the table. */
+int64_t nplda_resample_chunk_table(const int64_t* out_off, int64_t n_utts, int32_t* table, int64_t capacity);
+/* One resampling call: utterances of different ratios, copies and empty ones in ONE launch (plus the launch that clears
+ * `clipped`); the launch count depends on the struct's counts only, nothing is read back, there is no memset, and the call
+ * can be captured in a graph.  NPLDA_EUNSUPPORTED before any launch: max_iu / max_ou > NPLDA_RESAMPLE_MAX_UNITS, max_taps >
+ * NPLDA_RESAMPLE_MAX_TAPS, max_span beyond NPLDA_RESAMPLE_MAX_LDS_BYTES, counts beyond the int32 indexing; NPLDA_EINVAL: a
+ * missing or misaligned pointer, a non-positive maximum.  n_utts == 0 is a no-op.  No floating-point atomics: the same bits
+ * on every call, and an utterance's bits do not depend on the batch, the chunking or the order. */
+int nplda_resample_batch(const nplda_resample_call* call, nplda_stream_t stream);
+
 /* ---- measurement utility ------------------------------------------------------------------------------------- */
 
 /* Shader-clock probe for bench.py (no reference counterpart): one wave that stays resident for window_us microseconds

@@ -290,6 +290,10 @@ SIGNATURES = {
     "nplda_augment_power_i64": (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp]),
     "nplda_augment_workspace_bytes": (_c_sz, [_c_i64] * 4),
     "nplda_augment_batch": (_c_int, [_c_vp, _c_vp, _c_sz, _c_vp]),
+    "nplda_resample_chunk": (_c_int, []),
+    "nplda_resample_span_floats": (_c_sz, [ctypes.c_int32] * 3),
+    "nplda_resample_chunk_table": (_c_i64, [_c_vp, _c_i64, _c_vp, _c_i64]),
+    "nplda_resample_batch": (_c_int, [_c_vp, _c_vp]),
     "nplda_class_scatter_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_int]),
     "nplda_class_scatter_f32": (_c_int, [_c_f32p, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp, _c_i64, _c_int, _c_f32p, _c_vp, _c_vp,
                                          _c_vp, _c_int, _c_vp, _c_sz, _c_vp]),

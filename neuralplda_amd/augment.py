@@ -19,10 +19,10 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib, kaldi_format
+from . import _lib, kaldi_format, resample as _resample
 
-__all__ = ["RirTable", "NoiseTable", "Recipe", "Augmenter", "augment", "prepare", "output_lengths", "workspace_bytes", "BLOCK",
-           "MAX_RIR"]
+__all__ = ["RirTable", "NoiseTable", "Recipe", "Augmenter", "augment", "prepare", "output_lengths", "perturbed_lengths",
+           "workspace_bytes", "BLOCK", "MAX_RIR"]
 
 BLOCK, TILE, GROUP, CHUNK, MAX_RIR = 256, 32, 8, 2048, 32768  # include/nplda_hip.h NPLDA_AUGMENT_*
 PSIZE = 2 * BLOCK
@@ -117,19 +117,32 @@ class _Plan:
 
 # ---- ragged tables -------------------------------------------------------------------------------------------------------
 
-def _load_items(items, sample_frequency, what):
-    out = []
+def _load_items(items, sample_frequency, what, resample=False, keep_dc=False):
+    """The items as arrays.  resample: wave files at another rate are brought to sample_frequency on the device, all in one
+    call: int16 again, or (keep_dc) float32 times rate / sample_frequency, so that the sum of the taps stays what it was."""
+    out, other = [], []
     for i, it in enumerate(items):
         if isinstance(it, (str, bytes)) or hasattr(it, "__fspath__"):
             rate, x = kaldi_format.read_wav(it)
             if rate != int(sample_frequency):
-                raise ValueError(f"{what} {i} ({it}): sample rate {rate}, expected {int(sample_frequency)}")
+                if not resample:
+                    raise ValueError(f"{what} {i} ({it}): sample rate {rate}, expected {int(sample_frequency)}")
+                _resample.check_ratio(rate, int(sample_frequency), who=f"{what} {i} ({it})")
+                other.append((i, rate))
             out.append(x)
         else:
             a = np.asarray(it)
             if a.ndim != 1:
                 raise ValueError(f"{what} {i}: expected a one-dimensional array")
             out.append(a)
+    if other:
+        rates = np.array([r for _, r in other], dtype=np.int64)
+        y, yo, _ = _resample.resample(np.concatenate([out[i] for i, _ in other]), _cum([len(out[i]) for i, _ in other]), rates,
+                                      int(sample_frequency), gain=rates / float(int(sample_frequency)) if keep_dc else 1.0,
+                                      out_dtype=torch.float32 if keep_dc else torch.int16)
+        y = y.cpu().numpy()
+        for k, (i, _) in enumerate(other):
+            out[i] = y[yo[k]:yo[k + 1]]
     return out
 
 
@@ -142,11 +155,15 @@ def early_window(h, sample_frequency):
 
 class RirTable:
     """Room impulse responses: float32, ragged, each of 1 .. 32 768 taps; from arrays or 16-bit wave files (the counts as
-    float32, unscaled).  The spectra of every response and of its early window are computed once per device."""
+    float32, unscaled).  The spectra of every response and of its early window are computed once per device.  resample: a
+    wave file at another rate is resampled once, here, on the current device (neuralplda_amd.resample); the result stays
+    float32 (it is not rounded back to 16 bits) and is scaled by rate / sample_frequency, so that the response keeps its DC
+    gain — the sum of its taps — at the new rate.  Without it such a file is a ValueError."""
 
-    def __init__(self, arrays_or_wav_paths, sample_frequency):
+    def __init__(self, arrays_or_wav_paths, sample_frequency, resample=False):
         self.sample_frequency = float(sample_frequency)
-        hs = [np.ascontiguousarray(a, dtype=np.float32) for a in _load_items(arrays_or_wav_paths, sample_frequency, "RIR")]
+        hs = [np.ascontiguousarray(a, dtype=np.float32)
+              for a in _load_items(arrays_or_wav_paths, sample_frequency, "RIR", resample, keep_dc=True)]
         for r, h in enumerate(hs):
             if len(h) < 1:
                 raise ValueError(f"RIR {r}: empty")
@@ -201,11 +218,12 @@ class RirTable:
 class NoiseTable:
     """Noise items: int16, ragged; from arrays or 16-bit wave files.  `labels`: one of "noise", "music", "babble" per item
     (what an Augmenter may use it for); None: every item serves every kind.  The items' exact sums of squares are computed
-    once per device."""
+    once per device.  resample: a wave file at another rate is resampled once, here, on the current device
+    (neuralplda_amd.resample) and rounded back to int16; without it such a file is a ValueError."""
 
-    def __init__(self, arrays_or_wav_paths, sample_frequency, labels=None):
+    def __init__(self, arrays_or_wav_paths, sample_frequency, labels=None, resample=False):
         self.sample_frequency = float(sample_frequency)
-        xs = _load_items(arrays_or_wav_paths, sample_frequency, "noise item")
+        xs = _load_items(arrays_or_wav_paths, sample_frequency, "noise item", resample)
         for i, x in enumerate(xs):
             if x.dtype != np.int16:
                 raise ValueError(f"noise item {i}: expected int16 samples (the values as they are, not scaled)")
@@ -253,15 +271,18 @@ class NoiseTable:
 class Recipe:
     """What to do with each of U utterances, as plain arrays: rir (U,) int, -1 for none; additive: U lists of (noise item,
     start sample in the output, snr_db, repeat); shift_output, normalize_output (U,) bool, default true; volume (U,) float,
-    default 0 (a positive value is the gain and switches normalisation off)."""
+    default 0 (a positive value is the gain and switches normalisation off); speed (U,) float, default 1: the utterance is
+    first made `speed` times as fast (resample.speed_perturb: 1 / speed as long, shifted in pitch), and everything else —
+    the additive entries' start samples too — refers to the perturbed utterance."""
 
-    def __init__(self, rir, additive=None, shift_output=True, normalize_output=True, volume=0.0):
+    def __init__(self, rir, additive=None, shift_output=True, normalize_output=True, volume=0.0, speed=1.0):
         self.rir = np.array(rir, dtype=np.int64).reshape(-1)
         U = len(self.rir)
         self.additive = [[] for _ in range(U)] if additive is None else [[tuple(e) for e in ent] for ent in additive]
         self.shift_output = np.broadcast_to(np.asarray(shift_output, dtype=bool), (U,)).copy()
         self.normalize_output = np.broadcast_to(np.asarray(normalize_output, dtype=bool), (U,)).copy()
         self.volume = np.broadcast_to(np.asarray(volume, dtype=np.float32), (U,)).copy()
+        self.speed = np.broadcast_to(np.asarray(speed, dtype=np.float64), (U,)).copy()
         if len(self.additive) != U:
             raise ValueError(f"Recipe: {len(self.additive)} additive lists for {U} utterances")
 
@@ -276,7 +297,11 @@ class Recipe:
     def select(self, idx):
         idx = np.asarray(idx, dtype=np.int64)
         return Recipe(self.rir[idx], [self.additive[i] for i in idx], self.shift_output[idx], self.normalize_output[idx],
-                      self.volume[idx])
+                      self.volume[idx], self.speed[idx])
+
+    def at_unit_speed(self):
+        """The same recipe for utterances that are already perturbed."""
+        return Recipe(self.rir, self.additive, self.shift_output, self.normalize_output, self.volume)
 
     def validate(self, lengths, rirs, noises):
         """ValueError naming the utterance for an index outside its table or a malformed entry."""
@@ -289,6 +314,8 @@ class Recipe:
                 raise ValueError(f"utterance {u}: RIR {r} outside the table of {R}")
             if not np.isfinite(self.volume[u]):
                 raise ValueError(f"utterance {u}: volume {self.volume[u]}")
+            if not (np.isfinite(self.speed[u]) and self.speed[u] > 0):
+                raise ValueError(f"utterance {u}: speed {self.speed[u]}")
             for e in self.additive[u]:
                 if len(e) != 4:
                     raise ValueError(f"utterance {u}: an additive entry is (noise item, start, snr_db, repeat), got {e!r}")
@@ -301,17 +328,40 @@ class Recipe:
                     raise ValueError(f"utterance {u}: snr_db {snr}")
 
 
-def output_lengths(lengths, recipe, rirs):
-    """Samples out per utterance: n with shift_output or without a RIR, else n + L - 1 (host arithmetic)."""
+def _sample_frequency(sample_frequency, rirs, noises=None):
+    for sr in (sample_frequency, getattr(rirs, "sample_frequency", None), getattr(noises, "sample_frequency", None)):
+        if sr is not None:
+            return int(sr)
+    raise ValueError("a recipe with a speed other than 1 needs sample_frequency (or a table that carries it)")
+
+
+def perturbed_lengths(lengths, recipe, sample_frequency):
+    """Samples per utterance after the recipe's speed perturbation, ceil(n sr / round(speed sr)): host arithmetic."""
     n = np.asarray(lengths, dtype=np.int64)
+    if (recipe.speed == 1.0).all():
+        return n
+    sr = int(sample_frequency)
+    return _resample.output_lengths(n, _resample.speed_rates(recipe.speed, sr, len(recipe)), sr)
+
+
+def _perturbed(lengths, recipe, rirs, sample_frequency):
+    if (recipe.speed == 1.0).all():
+        return np.asarray(lengths, dtype=np.int64), recipe
+    return perturbed_lengths(lengths, recipe, _sample_frequency(sample_frequency, rirs)), recipe.at_unit_speed()
+
+
+def output_lengths(lengths, recipe, rirs, sample_frequency=None):
+    """Samples out per utterance: with n the length after the recipe's speed perturbation, n with shift_output or without
+    a RIR, else n + L - 1 (host arithmetic)."""
+    n, recipe = _perturbed(lengths, recipe, rirs, sample_frequency)
     has = (recipe.rir >= 0) & (n > 0)   # the convolution of no samples is no samples
     L = np.where(has, rirs.lengths[np.where(has, recipe.rir, 0)], 1) if has.any() else np.ones_like(n)
     return np.where(has & ~recipe.shift_output, n + L - 1, n)
 
 
-def _layout(lengths, recipe, rirs):
-    """The host arithmetic of a call: counts of blocks, groups and chunks per utterance."""
-    n = np.asarray(lengths, dtype=np.int64)
+def _layout(lengths, recipe, rirs, sample_frequency=None):
+    """The host arithmetic of a call: counts of blocks, groups and chunks per utterance (of the perturbed lengths)."""
+    n, recipe = _perturbed(lengths, recipe, rirs, sample_frequency)
     has = (recipe.rir >= 0) & (n > 0)
     ridx = np.where(has, recipe.rir, 0)
     L = np.where(has, rirs.lengths[ridx], 0) if has.any() else np.zeros_like(n)
@@ -321,9 +371,10 @@ def _layout(lengths, recipe, rirs):
                 n_out=output_lengths(n, recipe, rirs) if has.any() else n.copy())
 
 
-def workspace_bytes(lengths, recipe, rirs=None):
-    """Bytes of workspace of one call on these utterances (host arithmetic, nplda_augment_workspace_bytes)."""
-    lay = _layout(lengths, recipe, rirs)
+def workspace_bytes(lengths, recipe, rirs=None, sample_frequency=None):
+    """Bytes of workspace of one call on these utterances (host arithmetic, nplda_augment_workspace_bytes; the speed
+    perturbation in front of it takes none)."""
+    lay = _layout(lengths, recipe, rirs, sample_frequency)
     E = sum(len(e) for e in recipe.additive)
     return int(_lib.load().nplda_augment_workspace_bytes(len(recipe), E, int(lay["blocks"].sum()),
                                                          int(_ceil_div(lay["n_out"], CHUNK).sum())))
@@ -428,8 +479,9 @@ class Prepared:
     (one per piece of the batch) run one after the other on the current stream and share ONE workspace of the largest
     piece's size, `workspace_bytes`: that, not the sum over the pieces, is what the batch holds on the device."""
 
-    def __init__(self, calls, samples, offsets, clipped, device):
+    def __init__(self, calls, samples, offsets, clipped, device, speed=None):
         self.calls, self.samples, self.offsets, self.clipped, self.device = calls, samples, offsets, clipped, device
+        self.speed = speed   # the resample.Prepared of the speed perturbation in front of the calls, or None
         self.workspace_bytes = max([c.ws_bytes for c in calls], default=0)
         self.workspace = torch.empty(max(self.workspace_bytes, 256), dtype=torch.uint8, device=device)
         for c in calls:
@@ -437,15 +489,19 @@ class Prepared:
 
     def launch(self):
         with _lib.on_device(self.device):
+            if self.speed is not None:
+                self.speed.launch()
             for c in self.calls:
                 c.launch()
         return self.samples, self.offsets, self.clipped
 
 
-def prepare(samples, offsets, recipe, rirs=None, noises=None, out_dtype=torch.int16, device=None, workspace_limit=None):
+def prepare(samples, offsets, recipe, rirs=None, noises=None, out_dtype=torch.int16, device=None, workspace_limit=None,
+            sample_frequency=None):
     """Everything of augment() that touches the host — checks, output lengths, index arrays, workspace and output
     allocation, the tables' device copies — done once; the result's launch() only enqueues kernels (the same count for the
-    same shapes), so it can be captured in a graph."""
+    same shapes), so it can be captured in a graph.  With a speed other than 1 in the recipe, one resample launch (16-bit,
+    unit gain) goes in front of the pieces, which then work on the perturbed utterances."""
     if out_dtype not in (torch.int16, torch.float32):
         raise ValueError("out_dtype: torch.int16 or torch.float32")
     if torch.is_tensor(offsets):
@@ -465,6 +521,12 @@ def prepare(samples, offsets, recipe, rirs=None, noises=None, out_dtype=torch.in
         raise ValueError("offsets: expected U + 1 non-decreasing sample offsets inside the samples")
     lengths = np.diff(offs)
     recipe.validate(lengths, rirs, noises)
+    speed = None
+    if (recipe.speed != 1.0).any():
+        sr = _sample_frequency(sample_frequency, rirs, noises)
+        speed = _resample.prepare(samples, offs, _resample.speed_rates(recipe.speed, sr, U), sr, device=dev)
+        samples, offs, recipe = speed.samples, speed.offsets, recipe.at_unit_speed()
+        lengths = np.diff(offs)
     lay = _layout(lengths, recipe, rirs)
     for u in range(U):
         if max(int(lay["conv"][u]), int(lengths[u])) > np.iinfo(np.int32).max - PSIZE:
@@ -480,16 +542,18 @@ def prepare(samples, offsets, recipe, rirs=None, noises=None, out_dtype=torch.in
         calls = [PreparedCall(d_samples, offs[lo:hi + 1], recipe.select(np.arange(lo, hi)), rirs, noises, out,
                               out_offs[lo:hi + 1], clipped[lo:hi], dev)
                  for lo, hi in _pieces(lengths, recipe, rirs, int(workspace_limit)) if hi > lo]
-        return Prepared(calls, out, out_offs, clipped, dev)
+        return Prepared(calls, out, out_offs, clipped, dev, speed)
 
 
-def augment(samples, offsets, recipe, rirs=None, noises=None, out_dtype=torch.int16, device=None, workspace_limit=None):
+def augment(samples, offsets, recipe, rirs=None, noises=None, out_dtype=torch.int16, device=None, workspace_limit=None,
+            sample_frequency=None):
     """samples: int16 tensor or array holding every utterance; offsets: U + 1 sample offsets on the HOST; recipe: a Recipe of U
     utterances -> (samples' on the device in out_dtype (torch.int16 or torch.float32), offsets' int64 on the host, clipped
     (U,) int32 on the device: the samples that saturated, zero for float output).  The output lengths are host arithmetic:
     nothing is read back.  A batch whose workspace would exceed workspace_limit (default xvector.MAX_WORKSPACE_BYTES) is split
-    by whole utterances; the split does not change a bit.  Argument errors are ValueErrors naming the utterance."""
-    return prepare(samples, offsets, recipe, rirs, noises, out_dtype, device, workspace_limit).launch()
+    by whole utterances; the split does not change a bit.  Argument errors are ValueErrors naming the utterance.  A recipe
+    with speeds other than 1 resamples those utterances first (sample_frequency: that of the audio; default: the tables')."""
+    return prepare(samples, offsets, recipe, rirs, noises, out_dtype, device, workspace_limit, sample_frequency).launch()
 
 
 # ---- drawing recipes -----------------------------------------------------------------------------------------------------
@@ -503,6 +567,9 @@ NOISE_GAP_SECONDS = 1.0
 class Augmenter:
     """Draws recipes on the host from numpy.random.Generator(PCG64(seed)), with the kinds of the Kaldi voxceleb recipe; a
     seed repeats a run.  design/k28_augment.md states the draw step by step.  Per utterance, in order:
+      with speeds (a tuple such as (0.9, 1.0, 1.1)): speed = speeds[integers(len(speeds))], and n becomes the perturbed
+              length ceil(n sr / round(speed sr)); with speeds=None nothing is drawn here and the recipes are those of an
+              Augmenter without the argument
       kind = kinds[integers(len(kinds))]
       clean:  nothing
       reverb: rir = integers(number of RIRs)
@@ -511,9 +578,10 @@ class Augmenter:
       music:  item = music items[integers(count)], snr = (15, 10, 8, 5)[integers(4)], entry (item, 0, snr, repeat)
       babble: k = integers(3, 8); k times: item = babble items[integers(count)], snr = (20, 17, 15, 13)[integers(4)],
               entry (item, 0, snr, repeat)
-    Every recipe has shift_output and normalize_output on and volume 0."""
+    Every recipe has shift_output and normalize_output on and volume 0.  All draws of an utterance follow one another, so
+    the recipes do not depend on how the utterances are cut into calls of draw()."""
 
-    def __init__(self, rirs, noises, kinds=KINDS, seed=0):
+    def __init__(self, rirs, noises, kinds=KINDS, seed=0, speeds=None, sample_frequency=None):
         kinds = tuple(kinds)
         if not kinds or any(k not in KINDS for k in kinds):
             raise ValueError(f"kinds: a non-empty choice of {KINDS}")
@@ -530,12 +598,24 @@ class Augmenter:
         self.rirs, self.noises, self.kinds = rirs, noises, kinds
         self.rng = np.random.Generator(np.random.PCG64(seed))
         self.gap = int(NOISE_GAP_SECONDS * (noises.sample_frequency if noises is not None else 0))
+        self.speeds = None if speeds is None else tuple(float(f) for f in speeds)
+        self.sample_frequency = sample_frequency
+        if self.speeds is not None:
+            if not self.speeds:
+                raise ValueError("speeds: a non-empty tuple of speed factors, or None")
+            self.sample_frequency = sr = _sample_frequency(sample_frequency, rirs, noises)
+            for f, rate in zip(self.speeds, _resample.speed_rates(self.speeds, sr)):
+                _resample.check_ratio(int(rate), sr, who=f"speed {f}")
 
     def draw(self, lengths):
         """A Recipe for utterances of these lengths (the generator moves on: the next call draws the next recipes)."""
         rng = self.rng
-        rir, additive = [], []
+        rir, additive, speed = [], [], []
         for n in np.asarray(lengths, dtype=np.int64).reshape(-1):
+            if self.speeds is not None:
+                speed.append(self.speeds[int(rng.integers(len(self.speeds)))])
+                sr = self.sample_frequency
+                n = int(_resample.output_lengths(n, _resample.speed_rates(speed[-1], sr), sr))
             kind = self.kinds[int(rng.integers(len(self.kinds)))]
             r, ent = -1, []
             if kind == "reverb":
@@ -556,9 +636,10 @@ class Augmenter:
                     ent.append((item, 0, SNRS[kind][int(rng.integers(4))], True))
             rir.append(r)
             additive.append(ent)
-        return Recipe(rir, additive)
+        return Recipe(rir, additive, speed=speed if self.speeds is not None else 1.0)
 
     def __call__(self, samples, offsets, out_dtype=torch.int16, device=None):
         """Draw a recipe for these utterances and apply it: augment(...)'s three results."""
         offs = np.asarray(offsets.cpu().numpy() if torch.is_tensor(offsets) else offsets, dtype=np.int64).ravel()
-        return augment(samples, offs, self.draw(np.diff(offs)), self.rirs, self.noises, out_dtype, device)
+        return augment(samples, offs, self.draw(np.diff(offs)), self.rirs, self.noises, out_dtype, device,
+                       sample_frequency=self.sample_frequency)

@@ -659,15 +659,16 @@ def write_wav(path, samples, sample_frequency):
         fh.write(x.astype("<i2").tobytes())
 
 
-def load_wav_scp(path, entries=None, sample_frequency=None, channel=0):
+def load_wav_scp(path, entries=None, sample_frequency=None, channel=0, return_rates=False):
     """Kaldi wav.scp -> (keys, offsets int64 (U + 1), samples int16): the chosen channel of every file, one after the other
     in ONE buffer; utterance u is samples[offsets[u]:offsets[u + 1]].  `entries`: a slice of read_scp(path) to load instead
     of the whole file.  An entry that is a command pipe (ends in `|`), a file that is not 16-bit PCM, a truncated data
     chunk, or (if given) a sample rate other than sample_frequency is a KaldiFormatError naming the key.  `segments` files
-    are not read."""
+    are not read.  return_rates: a fourth result, the (U,) int64 sample rates of the files (with sample_frequency=None files
+    of any rate are loaded: neuralplda_amd.resample brings them to one)."""
     if entries is None:
         entries = read_scp(path)
-    layout, offsets = [], np.zeros(len(entries) + 1, dtype=np.int64)
+    layout, offsets, rates = [], np.zeros(len(entries) + 1, dtype=np.int64), np.zeros(len(entries), dtype=np.int64)
     for i, (key, rx) in enumerate(entries):
         if _is_pipe(rx):
             raise KaldiFormatError(f"{key}: command pipes in a wav.scp are not read ({rx.strip()!r})")
@@ -680,11 +681,12 @@ def load_wav_scp(path, entries=None, sample_frequency=None, channel=0):
         if sample_frequency is not None and rate != int(sample_frequency):
             raise KaldiFormatError(f"{key}: sample rate {rate}, expected {int(sample_frequency)} (there is no resampling)")
         layout.append(_wav_channel(buf, body, frames, ch, channel, key))
-        offsets[i + 1] = offsets[i] + frames
+        offsets[i + 1], rates[i] = offsets[i] + frames, rate
     samples = np.empty(int(offsets[-1]), dtype=np.int16)
     for i, src in enumerate(layout):
         samples[offsets[i]:offsets[i + 1]] = src
-    return [k for k, _ in entries], offsets, samples
+    keys = [k for k, _ in entries]
+    return (keys, offsets, samples, rates) if return_rates else (keys, offsets, samples)
 
 
 # ---- Kaldi initialisation of the model classes --------------------------------------------------------------------

@@ -535,7 +535,7 @@ class XVectorNet_ETDNN_12Layer(nn.Module):
         return keys, (parts[0] if len(parts) == 1 else torch.cat(parts)), dropped
 
     def extract_from_wav_scp(self, wav_scp, mfcc=None, vad=features.VadOptions(), cmn_window=300, min_frames=25,
-                             utts_per_call=256, device=None, channel=0, augmenter=None):
+                             utts_per_call=256, device=None, channel=0, augmenter=None, resample=False):
         """The whole front of the recipe over a Kaldi wav.scp of 16-bit PCM files: `compute-mfcc-feats --dither=0 |
         compute-vad-energy | apply-cmvn-sliding | select-voiced-frames | nnet3-xvector-compute`, nothing leaving the
         device in between -> (keys, (len(keys), 512) x-vectors on the device, dropped), as extract_from_scp.  mfcc: an
@@ -543,7 +543,9 @@ class XVectorNet_ETDNN_12Layer(nn.Module):
         vad: features.VadOptions, a {key: 0/1 vector} dict, or None.  The scp is worked through utts_per_call lines at a
         time; the pieces do not change the result (bit for bit).  augmenter: an augment.Augmenter; each piece is then
         augmented on the device (reverberation, noise, music, babble as it draws them for the piece's utterances, in scp
-        order) before its MFCCs; None leaves the audio as it is.  Inference only."""
+        order) before its MFCCs; None leaves the audio as it is.  resample: files at another rate than
+        mfcc.sample_frequency are resampled on the device (neuralplda_amd.resample) instead of being an error.  Inference
+        only."""
         from . import mfcc as _mfcc
         if mfcc is None:
             mfcc = _mfcc.MfccOptions(sample_frequency=16000, num_mel_bins=30, num_ceps=30, low_freq=20, high_freq=7600,
@@ -562,8 +564,15 @@ class XVectorNet_ETDNN_12Layer(nn.Module):
         keys, dropped, parts = [], [], []
         for lo in range(0, len(entries), int(utts_per_call)):
             piece = entries[lo:lo + int(utts_per_call)]
-            pkeys, offsets, samples = kaldi_format.load_wav_scp(wav_scp, entries=piece,
-                                                                sample_frequency=mfcc.sample_frequency, channel=channel)
+            if resample:
+                pkeys, offsets, samples, rates = kaldi_format.load_wav_scp(wav_scp, entries=piece, channel=channel,
+                                                                           return_rates=True)
+                if (rates != int(mfcc.sample_frequency)).any():
+                    from . import resample as _resample
+                    samples, offsets, _ = _resample.resample(samples, offsets, rates, int(mfcc.sample_frequency), device=dev)
+            else:
+                pkeys, offsets, samples = kaldi_format.load_wav_scp(wav_scp, entries=piece,
+                                                                    sample_frequency=mfcc.sample_frequency, channel=channel)
             if augmenter is not None:
                 samples, offsets, _ = augmenter(samples, offsets, device=dev)
             frames, lengths = _mfcc.compute_mfcc(samples, offsets, mfcc, dev)
