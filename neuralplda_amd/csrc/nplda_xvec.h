@@ -28,6 +28,7 @@ constexpr int kFeatP = 32;
 constexpr int kContext = 22;  // frames an utterance loses through the stack: 4 + 4 + 6 + 8
 constexpr int kRowSlack = 16; // rows past the last tile a layer may read (max d (c - 1) = 8)
 constexpr int kPoolDim = 1500;
+constexpr int kPoolLd = 16 * ((kPoolDim + 15) / 16);  // out_ld(kTdnn - 1) for device code (the windows pooling kernel)
 constexpr int kPooledLd = 3008;
 constexpr int kEmbDim = 512;
 
@@ -72,5 +73,17 @@ inline size_t packed_floats() {
     for (int l = 0; l < kLayers; ++l) o = geom(l, o).end;
     return o;
 }
+
+// layer l inside the packed image
+inline LayerGeom geomF(int l) {
+    size_t o = 0;
+    for (int i = 0; i < l; ++i) o = geom(i, o).end;
+    return geom(l, o);
+}
+
+// ---- workspace arithmetic shared by extraction and the two training paths ------------------------------------------
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+inline long long whole_tiles(long long n) { return (n + kRowsPerBlock - 1) / kRowsPerBlock * kRowsPerBlock; }
+inline int out_ld(int l) { return l == kTdnn - 1 ? kPoolLd : kEmbDim; }  // row stride of tdnn<l+1>'s output
 
 }  // namespace nplda_xvec

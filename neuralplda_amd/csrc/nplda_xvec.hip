@@ -23,7 +23,9 @@
 //  * xvec_pool_windows_kernel  the same pooling over a table of (overlapping) row windows of ONE dense pass: sliding-window
 //                         x-vectors without running a frame through the layers once per window (design/k23).
 // The GEMM body, xvec_prep_kernel and xvec_pool_kernel live in nplda_xvec_body.h, shared with the training forward and
-// backward (nplda_xvec_bwd.hip).
+// backward (nplda_xvec_bwd.hip), and so do the host pieces the family shares: gemm_args, launch_gemm and the argument
+// checks of a forward entry point (check_forward); the workspace arithmetic (align256, whole_tiles, out_ld, geomF) is
+// nplda_xvec.h's.
 #include "nplda_xvec_body.h"
 
 namespace {
@@ -62,43 +64,23 @@ struct WsLayout {
     size_t o0, oA, oB, oP, total;  // bytes
 };
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 WsLayout ws_layout(long long R, long long U) {
     WsLayout w;
-    w.rows = (R + kRowsPerBlock - 1) / kRowsPerBlock * kRowsPerBlock + kRowSlack;
-    w.urows = (U + kRowsPerBlock - 1) / kRowsPerBlock * kRowsPerBlock;
+    w.rows = whole_tiles(R) + kRowSlack;
+    w.urows = whole_tiles(U);
     w.o0 = 0;
     w.oA = align256(w.o0 + (size_t)w.rows * kFeatP * 4);
     w.oB = align256(w.oA + (size_t)w.rows * kEmbDim * 4);
-    w.oP = align256(w.oB + (size_t)w.rows * 16 * ((kPoolDim + 15) / 16) * 4);
+    w.oP = align256(w.oB + (size_t)w.rows * out_ld(kTdnn - 1) * 4);
     w.total = align256(w.oP + (size_t)w.urows * kPooledLd * 4);
     return w;
 }
 
 int launch_layer(int l, const float* packed, const float* in, long long ld_in, long long rows, float* out,
                  long long ld_out, long long row_limit, hipStream_t st) {
-    size_t o = 0;
-    LayerGeom G = geom(0, 0);
-    for (int i = 0; i <= l; ++i) {
-        G = geom(i, o);
-        o = G.end;
-    }
-    GemmArgs a;
-    a.in = in; a.ld_in = ld_in;
-    a.frag = reinterpret_cast<const f32x4*>(packed + G.oFrag);
-    a.bias = packed + G.oBias; a.mean = packed + G.oMean; a.inv = packed + G.oInv;
-    a.out = out; a.ld_out = ld_out; a.row_limit = row_limit;
-    a.nkb = G.nkb; a.nkbp = G.nkbp; a.XBp = G.XBp; a.Np = G.Np; a.kbt = G.Dinp / 16; a.dil = G.d;
-    a.relu_bn = l < kTdnn ? 1 : 0;
-    const long long tiles = rows / kRowsPerBlock;
-    if (tiles <= 0) return NPLDA_OK;
-    if (tiles > 0x7fffffffLL) return NPLDA_EINVAL;
-    hipLaunchKernelGGL(xvec_gemm_kernel, dim3((unsigned)tiles, (unsigned)(G.XBp / kNS)), dim3(256), 0, st, a);
-    return nplda_launch_status();
+    const GemmArgs a = gemm_args(packed, geomF(l), in, ld_in, out, ld_out, row_limit, kShape[l].d, l < kTdnn ? 1 : 0);
+    return launch_gemm(xvec_gemm_kernel, a, rows, st);
 }
-
-constexpr int kPoolLd = 16 * ((kPoolDim + 15) / 16);  // row stride of the tdnn10 output
 
 // lin11 over the n pooled rows (prows of them allocated: whole tiles, the padding rows zeroed)
 int lin11(const float* P, float* pooled, long long n, long long prows, float* out, long long ldx, hipStream_t st) {
@@ -119,16 +101,16 @@ int dense_pass(const float* x, int layout, long long ld_in, long long T, long lo
                        total_frames, w.rows, b0);
     if (int rc = nplda_launch_status()) return rc;
     // the slack rows of the activation buffers are read by the last tile's context taps (results discarded): zeroed
-    const long long live = w.rows - kRowSlack;
+    const long long live = w.rows - kRowSlack, ld10 = out_ld(kTdnn - 1);
     if (hipMemsetAsync(bA + live * kEmbDim, 0, (size_t)kRowSlack * kEmbDim * 4, st) != hipSuccess ||
         hipMemsetAsync(bB + live * kEmbDim, 0, (size_t)kRowSlack * kEmbDim * 4, st) != hipSuccess ||
-        hipMemsetAsync(bB + live * kPoolLd, 0, (size_t)kRowSlack * kPoolLd * 4, st) != hipSuccess)
+        hipMemsetAsync(bB + live * ld10, 0, (size_t)kRowSlack * ld10 * 4, st) != hipSuccess)
         return NPLDA_EINVAL;
     const float* in = b0;
     long long ld = kFeatP;
     for (int l = 0; l < kTdnn; ++l) {
         float* o = (l & 1) ? bB : bA;
-        const long long ldo = l == kTdnn - 1 ? kPoolLd : kEmbDim;
+        const long long ldo = out_ld(l);
         if (int rc = launch_layer(l, P, in, ld, live, o, ldo, live, st)) return rc;
         in = o;
         ld = ldo;
@@ -234,15 +216,10 @@ size_t nplda_xvec_workspace_bytes(int64_t total_frames, int64_t n_utts) {
 int nplda_xvec_extract_f32(const float* x, int layout, int64_t ld_in, const int64_t* offsets, int64_t n_utts,
                            int64_t total_frames, int pooling, const void* packed, float* out, int64_t ldx, void* ws,
                            size_t ws_bytes, nplda_stream_t stream) {
-    if (n_utts < 0 || total_frames < 0) return NPLDA_EINVAL;
-    if (layout != NPLDA_XVEC_LAYOUT_ROWS && layout != NPLDA_XVEC_LAYOUT_BCT) return NPLDA_EINVAL;
-    if (pooling != NPLDA_XVEC_POOL_STD && pooling != NPLDA_XVEC_POOL_VAR) return NPLDA_EINVAL;
-    if (n_utts == 0) return NPLDA_OK;
-    if (!x || !offsets || !packed || !out || !ws || !nplda_aligned16(packed) || !nplda_aligned16(out) ||
-        !nplda_aligned16(ws) || ldx < kEmbDim || (ldx % 4) != 0)
-        return NPLDA_EINVAL;
-    if (layout == NPLDA_XVEC_LAYOUT_ROWS && ld_in < kFeat) return NPLDA_EINVAL;
-    if (layout == NPLDA_XVEC_LAYOUT_BCT && (total_frames % n_utts) != 0) return NPLDA_EINVAL;
+    bool nothing;
+    const int bad = check_forward(n_utts, total_frames, layout, pooling, ld_in, ldx, {x, offsets, packed, out, ws},
+                                 {packed, out, ws}, &nothing);
+    if (bad || nothing) return bad;
     if (n_utts > 0x7fffffffLL / kPoolBlocks) return NPLDA_EUNSUPPORTED;
     const WsLayout w = ws_layout(total_frames, n_utts);
     if (ws_bytes < w.total) return NPLDA_ENOSPC;
@@ -254,7 +231,7 @@ int nplda_xvec_extract_f32(const float* x, int layout, int64_t ld_in, const int6
     const float* h;
     if (int rc = dense_pass(x, layout, ld_in, T, total_frames, w, base, P, st, &h)) return rc;
     hipLaunchKernelGGL(xvec_pool_kernel, dim3((unsigned)(n_utts * kPoolBlocks)), dim3(256), 0, st, h,
-                       (long long)kPoolLd, offsets, (long long)total_frames, pooling, pooled);
+                       (long long)out_ld(kTdnn - 1), offsets, (long long)total_frames, pooling, pooled);
     if (int rc = nplda_launch_status()) return rc;
     return lin11(P, pooled, n_utts, w.urows, out, ldx, st);
 }
@@ -267,12 +244,10 @@ size_t nplda_xvec_windows_workspace_bytes(int64_t total_frames, int64_t n_window
 int nplda_xvec_extract_windows_f32(const float* x, int64_t ld_in, int64_t total_frames, const int64_t* win_begin,
                                    const int64_t* win_end, int64_t n_windows, int pooling, const void* packed, float* out,
                                    int64_t ldx, void* ws, size_t ws_bytes, nplda_stream_t stream) {
-    if (n_windows < 0 || total_frames < 0) return NPLDA_EINVAL;
-    if (pooling != NPLDA_XVEC_POOL_STD && pooling != NPLDA_XVEC_POOL_VAR) return NPLDA_EINVAL;
-    if (n_windows == 0) return NPLDA_OK;
-    if (!x || !win_begin || !win_end || !packed || !out || !ws || !nplda_aligned16(packed) || !nplda_aligned16(out) ||
-        !nplda_aligned16(ws) || ldx < kEmbDim || (ldx % 4) != 0 || ld_in < kFeat)
-        return NPLDA_EINVAL;
+    bool nothing;
+    const int bad = check_forward(n_windows, total_frames, NPLDA_XVEC_LAYOUT_ROWS, pooling, ld_in, ldx,
+                                 {x, win_begin, win_end, packed, out, ws}, {packed, out, ws}, &nothing);
+    if (bad || nothing) return bad;
     if (n_windows > 0x7fffffffLL / kWinPoolBlocks) return NPLDA_EUNSUPPORTED;
     const WsLayout w = ws_layout(total_frames, n_windows);
     if (ws_bytes < w.total) return NPLDA_ENOSPC;

@@ -2,7 +2,8 @@
 // XVectorNet_ETDNN_12Layer.extract (utils/models.py:170-186) under a plain model.train(), where each tdnn is unfold,
 // Linear, ReLU, nn.BatchNorm1d(affine=False) on the statistics of the batch (utils/models.py:90-93).  The GEMMs, the
 // weight gradient, the bias sums, pooling and lin11 are those of the running-statistics path (nplda_xvec_body.h,
-// nplda_xvec_bwd.hip); this file adds the memory-bound part around them (design/k27_xvec_batch_stats.md).
+// nplda_xvec_bwd.hip), reached through the chains of nplda_xvec_train.h; this file adds the memory-bound part around
+// them (design/k27_xvec_batch_stats.md) and keeps its own two layer loops.
 //
 // V_l = rows whose index inside their utterance is < T_u - ctx_l (rem[row] > ctx_l), n_l = |V_l|.
 //
@@ -321,15 +322,6 @@ __global__ __launch_bounds__(256) void xvbn_pool_bwd_kernel(const float* __restr
 
 // ---- host helpers ----------------------------------------------------------------------------------------------
 
-template <class Epi>
-int launch_bn_gemm(const GemmArgs& a, long long rows, const Epi& e, hipStream_t st) {
-    const long long tiles = rows / kRowsPerBlock;
-    if (tiles <= 0) return NPLDA_OK;
-    if (tiles > 0x7fffffffLL) return NPLDA_EINVAL;
-    hipLaunchKernelGGL(xvbn_gemm_kernel<Epi>, dim3((unsigned)tiles, (unsigned)(a.XBp / kNS)), dim3(256), 0, st, a, e);
-    return nplda_launch_status();
-}
-
 template <bool kPair>
 int launch_sums(const float* x, long long ldx, const float* y, long long ldy, const int* rem, int ctx, long long nrows,
                 int S, int N, double* part, long long* cnt, hipStream_t st) {
@@ -369,15 +361,10 @@ int nplda_xvec_extract_train_bn_f32(const float* x, int layout, int64_t ld_in, c
                                     int64_t total_frames, int pooling, const void* packed, const float* eps, float* out,
                                     int64_t ldx, void* saved, size_t saved_bytes, void* stats, size_t stats_bytes_,
                                     nplda_stream_t stream) {
-    if (n_utts < 0 || total_frames < 0) return NPLDA_EINVAL;
-    if (layout != NPLDA_XVEC_LAYOUT_ROWS && layout != NPLDA_XVEC_LAYOUT_BCT) return NPLDA_EINVAL;
-    if (pooling != NPLDA_XVEC_POOL_STD && pooling != NPLDA_XVEC_POOL_VAR) return NPLDA_EINVAL;
-    if (n_utts == 0) return NPLDA_OK;
-    if (!x || !offsets || !packed || !eps || !out || !saved || !stats || !nplda_aligned16(packed) ||
-        !nplda_aligned16(out) || !nplda_aligned16(saved) || !nplda_aligned16(stats) || ldx < kEmbDim || (ldx % 4) != 0)
-        return NPLDA_EINVAL;
-    if (layout == NPLDA_XVEC_LAYOUT_ROWS && ld_in < kFeat) return NPLDA_EINVAL;
-    if (layout == NPLDA_XVEC_LAYOUT_BCT && (total_frames % n_utts) != 0) return NPLDA_EINVAL;
+    bool nothing;
+    const int bad = check_forward(n_utts, total_frames, layout, pooling, ld_in, ldx,
+                                  {x, offsets, packed, eps, out, saved, stats}, {packed, out, saved, stats}, &nothing);
+    if (bad || nothing) return bad;
     if (!enough_rows(total_frames, n_utts)) return NPLDA_EINVAL;
     if (bad_sizes(n_utts, total_frames)) return NPLDA_EUNSUPPORTED;
     const BnSavedLayout B = bn_saved_layout(total_frames, n_utts);
@@ -385,26 +372,14 @@ int nplda_xvec_extract_train_bn_f32(const float* x, int layout, int64_t ld_in, c
     if (saved_bytes < B.total || stats_bytes_ < stats_bytes()) return NPLDA_ENOSPC;
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)saved;
-    float* img = (float*)(base + L.oX);
-    int* rem = (int*)(base + L.oRem);
-    float* pooled = (float*)(base + L.oP);
+    const int* rem = (const int*)(base + L.oRem);
     double* part = (double*)(base + B.oPart);
     long long* cnt = (long long*)(base + B.oCnt);
     float* table = (float*)stats;
     long long* counts = (long long*)((char*)stats + stats_offset(kTdnn) * 4);
     const float* P = (const float*)packed;
-    const long long T = layout == NPLDA_XVEC_LAYOUT_BCT ? total_frames / n_utts : 0;
-    const long long n0 = L.rows * kFeatP;
-    hipLaunchKernelGGL(xvec_prep_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, x, layout,
-                       (long long)ld_in, T, (long long)total_frames, L.rows, img);
-    if (int rc = nplda_launch_status()) return rc;
-    if (int rc = launch_rem(offsets, n_utts, total_frames, L.rows, rem, st)) return rc;
-    // slack rows: read by the last tile's taps here and by the weight gradient's (finite zeros, never NaN patterns)
-    for (int l = 0; l < kTdnn; ++l)
-        if (hipMemsetAsync(base + L.oO[l] + (size_t)L.live * out_ld(l) * 4, 0, (size_t)kRowSlack * out_ld(l) * 4, st) !=
-            hipSuccess)
-            return NPLDA_EINVAL;
-    const float* in = img;
+    if (int rc = train_forward_head(x, layout, ld_in, offsets, n_utts, total_frames, L, base, st)) return rc;
+    const float* in = (const float*)(base + L.oX);
     long long ld = kFeatP;
     for (int l = 0; l < kTdnn; ++l) {
         const int N = out_ld(l);
@@ -413,7 +388,7 @@ int nplda_xvec_extract_train_bn_f32(const float* x, int layout, int64_t ld_in, c
         float* inv = (float*)(base + B.oInv[l]);
         const GemmArgs a = gemm_args(P, geomF(l), in, ld, o, N, L.live, kShape[l].d, 0);
         const EpiTrainRaw e{(uint8_t*)(base + L.oM[l]), (long long)N, rem, kCtx[l]};
-        if (int rc = launch_bn_gemm(a, L.live, e, st)) return rc;
+        if (int rc = launch_gemm(xvbn_gemm_kernel<EpiTrainRaw>, a, L.live, st, e)) return rc;
         if (int rc = launch_sums<false>(o, N, o, N, rem, kCtx[l], L.live, B.S, N, part, cnt, st)) return rc;
         hipLaunchKernelGGL(xvbn_stats_finish_kernel, dim3((unsigned)((N + kFinCols - 1) / kFinCols)),
                            dim3(kFinCols * kFinRuns), 0, st, part, cnt, B.S,
@@ -424,14 +399,7 @@ int nplda_xvec_extract_train_bn_f32(const float* x, int layout, int64_t ld_in, c
         in = o;
         ld = N;
     }
-    hipLaunchKernelGGL(xvec_pool_kernel, dim3((unsigned)(n_utts * kPoolBlocks)), dim3(256), 0, st, in, ld, offsets,
-                       (long long)total_frames, pooling, pooled);
-    if (int rc = nplda_launch_status()) return rc;
-    if (L.urows > n_utts &&
-        hipMemsetAsync(pooled + n_utts * kPooledLd, 0, (size_t)(L.urows - n_utts) * kPooledLd * 4, st) != hipSuccess)
-        return NPLDA_EINVAL;
-    const GemmArgs a = gemm_args(P, geomF(kTdnn), pooled, kPooledLd, out, ldx, n_utts, 1, 0);
-    return launch_gemm_extract(a, L.urows, st);
+    return train_forward_tail(P, offsets, n_utts, total_frames, pooling, L, base, out, ldx, st);
 }
 
 size_t nplda_xvec_backward_bn_workspace_bytes(int64_t total_frames, int64_t n_utts) {
@@ -442,68 +410,35 @@ size_t nplda_xvec_backward_bn_workspace_bytes(int64_t total_frames, int64_t n_ut
 int nplda_xvec_backward_bn_f32(const void* saved, size_t saved_bytes, const int64_t* offsets, int64_t n_utts,
                                int64_t total_frames, int pooling, const float* dxvec, int64_t lddx, const void* packed,
                                const void* packed_t, float* grad, void* ws, size_t ws_bytes, nplda_stream_t stream) {
-    if (n_utts < 0 || total_frames < 0) return NPLDA_EINVAL;
-    if (pooling != NPLDA_XVEC_POOL_STD && pooling != NPLDA_XVEC_POOL_VAR) return NPLDA_EINVAL;
-    if (n_utts == 0) return NPLDA_OK;
-    if (!saved || !offsets || !dxvec || !packed || !packed_t || !grad || !ws || !nplda_aligned16(saved) ||
-        !nplda_aligned16(packed) || !nplda_aligned16(packed_t) || !nplda_aligned16(grad) || !nplda_aligned16(ws) ||
-        lddx < kEmbDim)
-        return NPLDA_EINVAL;
+    bool nothing;
+    const int bad = check_backward(n_utts, total_frames, pooling, lddx, saved, offsets, dxvec, packed, packed_t, grad, ws,
+                                   &nothing);
+    if (bad || nothing) return bad;
     if (!enough_rows(total_frames, n_utts)) return NPLDA_EINVAL;
     if (bad_sizes(n_utts, total_frames)) return NPLDA_EUNSUPPORTED;
     const BnSavedLayout B = bn_saved_layout(total_frames, n_utts);
     const SavedLayout& L = B.base;
     const BnWsLayout BW = bn_bwd_layout(total_frames, n_utts);
-    const WsLayoutB& W = BW.base;
     if (saved_bytes < B.total || ws_bytes < BW.total) return NPLDA_ENOSPC;
     hipStream_t st = (hipStream_t)stream;
-    const char* sb = (const char*)saved;
+    const BwdBuffers b = bwd_buffers(L, BW.base, saved, ws);
+    const char* sb = b.sb;
     char* wb = (char*)ws;
     const float* PT = (const float*)packed_t;
-    float* dx = (float*)(wb + W.oDx);
-    float* dpool = (float*)(wb + W.oDp);
-    float* part = (float*)(wb + W.oPart);
-    double* colp = (double*)(wb + W.oCol);
     float* av = (float*)(wb + BW.oAC);
     float* cv = av + out_ld(kTdnn - 1);
     double* spart = (double*)(wb + BW.oPart);
     long long* cnt = (long long*)(wb + BW.oCnt);
     const int* rem = (const int*)(sb + L.oRem);
-    const float* pooled = (const float*)(sb + L.oP);
-    const long long U = n_utts, brow = kLead + L.rows;
-    // dxvec -> (urows, 512) zero-padded
-    if (hipMemcpy2DAsync(dx, kEmbDim * 4, dxvec, (size_t)lddx * 4, kEmbDim * 4, (size_t)U, hipMemcpyDeviceToDevice,
-                         st) != hipSuccess)
-        return NPLDA_EINVAL;
-    if (L.urows > U && hipMemsetAsync(dx + U * kEmbDim, 0, (size_t)(L.urows - U) * kEmbDim * 4, st) != hipSuccess)
-        return NPLDA_EINVAL;
-    // lin11: dW11 = dxvec^T pooled, db11 = sum dxvec, dpooled = dxvec W11
-    if (int rc = launch_wgrad(kTdnn, dx, kEmbDim, kEmbDim, pooled, kPooledLd, U, part, grad + grad_offset(kTdnn), st))
-        return rc;
-    if (int rc = launch_colsum(dx, kEmbDim, U, kEmbDim, colp,
-                               grad + grad_offset(kTdnn) + (size_t)kEmbDim * kShape[kTdnn].Din, st))
-        return rc;
-    {
-        const GemmArgs a = gemm_args(PT, geomT(kTdnn, packedT_offset(kTdnn)), dx, kEmbDim, dpool, kPooledLd, L.urows, 1, 0);
-        if (int rc = launch_gemm_extract(a, L.urows, st)) return rc;
-    }
+    float* dA;
+    long long ldA;
+    if (int rc = backward_head(b, L, n_utts, dxvec, lddx, PT, grad, st, &dA, &ldA)) return rc;
     // tdnn10: pooling backward into G_10 (every other row zero)
-    const int ld10 = out_ld(kTdnn - 1);
-    float* bufX = (float*)(wb + W.oX);
-    float* bufY = (float*)(wb + W.oY);
-    float* bufZ = (float*)(wb + W.oZ);
-    if (hipMemsetAsync(bufX, 0, (size_t)brow * ld10 * 4, st) != hipSuccess ||
-        hipMemsetAsync(bufY, 0, (size_t)kLead * kEmbDim * 4, st) != hipSuccess ||
-        hipMemsetAsync(bufZ, 0, (size_t)kLead * kEmbDim * 4, st) != hipSuccess)
-        return NPLDA_EINVAL;
-    float* dA = bufX + (size_t)kLead * ld10;
-    hipLaunchKernelGGL(xvbn_pool_bwd_kernel, dim3((unsigned)(U * kPoolBlocks)), dim3(256), 0, st,
-                       (const float*)(sb + L.oO[kTdnn - 1]), (long long)ld10, pooled, dpool, offsets,
-                       (long long)total_frames, pooling, dA);
+    hipLaunchKernelGGL(xvbn_pool_bwd_kernel, dim3((unsigned)(n_utts * kPoolBlocks)), dim3(256), 0, st,
+                       (const float*)(sb + L.oO[kTdnn - 1]), ldA, b.pooled, b.dpool, offsets, (long long)total_frames,
+                       pooling, dA);
     if (int rc = nplda_launch_status()) return rc;
-    long long ldA = ld10;
     for (int l = kTdnn - 1; l >= 0; --l) {
-        const Layer s = kShape[l];
         const int N = out_ld(l);
         const float* O = (const float*)(sb + L.oO[l]);
         // batch-norm and ReLU backward in place: G_l -> dA_l
@@ -516,18 +451,12 @@ int nplda_xvec_backward_bn_f32(const void* saved, size_t saved_bytes, const int6
                            (const uint8_t*)(sb + L.oM[l]), (long long)N, L.live, N, (const float*)(sb + B.oInv[l]), av,
                            cv);
         if (int rc = nplda_launch_status()) return rc;
-        const float* Oin = l == 0 ? (const float*)(sb + L.oX) : (const float*)(sb + L.oO[l - 1]);
-        const long long ldin = l == 0 ? kFeatP : out_ld(l - 1);
-        if (int rc = launch_wgrad(l, dA, ldA, (int)ldA, Oin, ldin, L.live, part, grad + grad_offset(l), st)) return rc;
-        if (int rc = launch_colsum(dA, ldA, L.live, s.Dout, colp, grad + grad_offset(l) + (size_t)s.Dout * s.c * s.Din,
-                                   st))
-            return rc;
+        if (int rc = layer_param_grads(l, dA, ldA, b, L, grad, st)) return rc;
         if (l == 0) break;
-        float* nxt = ((kTdnn - 1 - l) & 1 ? bufZ : bufY) + (size_t)kLead * kEmbDim;
-        const GemmArgs a = gemm_args(PT, geomT(l, packedT_offset(l)), dA, ldA, nxt, kEmbDim, L.live, -s.d, 0);
-        if (int rc = launch_bn_gemm(a, L.live, EpiStore{}, st)) return rc;
-        dA = nxt;
-        ldA = kEmbDim;
+        const GemmArgs a = data_grad_args(l, PT, dA, ldA, b, L.live);
+        if (int rc = launch_gemm(xvbn_gemm_kernel<EpiStore>, a, L.live, st, EpiStore{})) return rc;
+        dA = a.out;
+        ldA = a.ld_out;
     }
     return NPLDA_OK;
 }

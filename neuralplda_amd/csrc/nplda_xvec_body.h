@@ -1,12 +1,15 @@
-// nplda_xvec_gemm.h — the body of the E-TDNN GEMM (see nplda_xvec.hip for the design), templated on its epilogue so that
+// nplda_xvec_body.h — the body of the E-TDNN GEMM (see nplda_xvec.hip for the design), templated on its epilogue so that
 // the extraction kernel (nplda_xvec.hip, one instantiation) and the training forward / data-gradient kernels
-// (nplda_xvec_bwd.hip) run the same main loop and hence the same fp32 sums, bit for bit.
+// (nplda_xvec_bwd.hip, nplda_xvec_bn.hip) run the same main loop and hence the same fp32 sums, bit for bit; and the host
+// side every file of the family uses with it: gemm_args (a layer's GemmArgs), launch_gemm (the one grid computation) and
+// check_forward (the argument checks of the four forward entry points).
 //
 // An epilogue is a functor called once per (row group, 16-column block) with the accumulator of lane (j, g):
 //     epi(a, row, col, v)   row = r0 + 16 rg + j (< a.row_limit), col = 16 xb + 4 g (< a.Np), v = the four sums of
 //                           out[row, col .. col + 3] before bias.
 // A dilation may be negative: the data gradient gathers its taps at row - j d (the caller provides leading slack rows).
 #pragma once
+#include <initializer_list>
 #include "nplda_common.h"
 #include "nplda_xvec.h"
 
@@ -114,6 +117,61 @@ __device__ __forceinline__ void xvec_gemm_body(const GemmArgs& a, const Epi& epi
             epi(a, row, col, acc[rg][u]);
         }
     }
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------
+
+// layer geometry G inside the image `img` (packed, or the transposed image of the backward) -> the kernel's arguments
+inline GemmArgs gemm_args(const float* img, const LayerGeom& G, const float* in, long long ld_in, float* out,
+                          long long ld_out, long long row_limit, int dil, int relu_bn) {
+    GemmArgs a;
+    a.in = in; a.ld_in = ld_in;
+    a.frag = reinterpret_cast<const f32x4*>(img + G.oFrag);
+    a.bias = img + G.oBias; a.mean = img + G.oMean; a.inv = img + G.oInv;
+    a.out = out; a.ld_out = ld_out; a.row_limit = row_limit;
+    a.nkb = G.nkb; a.nkbp = G.nkbp; a.XBp = G.XBp; a.Np = G.Np; a.kbt = G.Dinp / 16; a.dil = dil;
+    a.relu_bn = relu_bn;
+    return a;
+}
+
+// `kernel` is a __global__ wrapper of xvec_gemm_body taking (GemmArgs, epilogue...): rows / 128 row tiles (rows is a
+// whole number of tiles) x the layer's column slices
+template <class Kernel, class... Epi>
+int launch_gemm(Kernel kernel, const GemmArgs& a, long long rows, hipStream_t st, const Epi&... e) {
+    const long long tiles = rows / kRowsPerBlock;
+    if (tiles <= 0) return NPLDA_OK;
+    if (tiles > 0x7fffffffLL) return NPLDA_EINVAL;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)tiles, (unsigned)(a.XBp / kNS)), dim3(256), 0, st, a, e...);
+    return nplda_launch_status();
+}
+
+inline bool none_null(std::initializer_list<const void*> ptrs) {
+    for (const void* p : ptrs)
+        if (!p) return false;
+    return true;
+}
+inline bool all_aligned16(std::initializer_list<const void*> ptrs) {
+    for (const void* p : ptrs)
+        if (!nplda_aligned16(p)) return false;
+    return true;
+}
+inline bool bad_pooling(int pooling) { return pooling != NPLDA_XVEC_POOL_STD && pooling != NPLDA_XVEC_POOL_VAR; }
+
+// The argument checks of a forward entry point (n utterances or windows), in the order that is part of the ABI; the
+// caller's grid limits (EUNSUPPORTED) and buffer sizes (ENOSPC) follow them, in that order.  *nothing: n == 0, return OK.
+inline int check_forward(int64_t n, int64_t total_frames, int layout, int pooling, int64_t ld_in, int64_t ldx,
+                         std::initializer_list<const void*> ptrs, std::initializer_list<const void*> aligned,
+                         bool* nothing) {
+    *nothing = false;
+    if (n < 0 || total_frames < 0) return NPLDA_EINVAL;
+    if (layout != NPLDA_XVEC_LAYOUT_ROWS && layout != NPLDA_XVEC_LAYOUT_BCT) return NPLDA_EINVAL;
+    if (bad_pooling(pooling)) return NPLDA_EINVAL;
+    *nothing = n == 0;
+    if (*nothing) return NPLDA_OK;
+    if (!none_null(ptrs) || !all_aligned16(aligned) || ldx < kEmbDim || (ldx % 4) != 0) return NPLDA_EINVAL;
+    if (layout == NPLDA_XVEC_LAYOUT_ROWS && ld_in < kFeat) return NPLDA_EINVAL;
+    if (layout == NPLDA_XVEC_LAYOUT_BCT && (total_frames % n) != 0) return NPLDA_EINVAL;
+    return NPLDA_OK;
 }
 
 }  // namespace nplda_xvec

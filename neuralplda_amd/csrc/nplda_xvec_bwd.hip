@@ -22,6 +22,7 @@
 //                                 over frames into per-split partials; xvbwd_reduce_kernel sums the splits in a fixed
 //                                 order and writes torch layout (Dout, c Din).  No atomics: two calls give equal bits.
 //  * xvbwd_colsum_kernel          bias gradients: per-split fp64 column sums, then a fixed-order finish.
+// The host chains both training paths run around their own layer loops (nplda_xvec_train.h) are defined here, once.
 #include "nplda_xvec_train.h"
 
 namespace {
@@ -260,26 +261,7 @@ __global__ void xvbwd_colsum_finish_kernel(const double* __restrict__ part, int 
 
 // ---- host helpers ----------------------------------------------------------------------------------------------
 
-template <class Epi>
-int launch_gemm(const GemmArgs& a, long long rows, const Epi& e, hipStream_t st) {
-    const long long tiles = rows / kRowsPerBlock;
-    if (tiles <= 0) return NPLDA_OK;
-    if (tiles > 0x7fffffffLL) return NPLDA_EINVAL;
-    hipLaunchKernelGGL(xvtr_gemm_kernel<Epi>, dim3((unsigned)tiles, (unsigned)(a.XBp / kNS)), dim3(256), 0, st, a, e);
-    return nplda_launch_status();
-}
-
-}  // namespace
-
-namespace nplda_xvec_train {
-
-int launch_rem(const int64_t* offsets, long long U, long long R, long long rows, int* rem, hipStream_t st) {
-    hipLaunchKernelGGL(xvtr_rem_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, offsets, U, R, rows, rem);
-    return nplda_launch_status();
-}
-
-int launch_gemm_extract(const GemmArgs& a, long long rows, hipStream_t st) { return launch_gemm(a, rows, EpiExtract{}, st); }
-
+// dW_l (torch layout) from dA rows and the layer's input rows: split-K partials in `part`, summed in split order
 int launch_wgrad(int l, const float* A, long long lda, int acols, const float* B, long long ldb, long long kmax,
                  float* part, float* out, hipStream_t st) {
     const Layer s = kShape[l];
@@ -297,6 +279,7 @@ int launch_wgrad(int l, const float* A, long long lda, int acols, const float* B
     return nplda_launch_status();
 }
 
+// out[col] = sum over nrows of A[:, col]: fp64 partials in `part` (kColSplits x N doubles at most), fixed order
 int launch_colsum(const float* A, long long lda, long long nrows, int N, double* part, float* out, hipStream_t st) {
     const long long want = (nrows + 255) / 256;  // at least 256 rows per split
     const int S = want < 1 ? 1 : (want > kColSplits ? kColSplits : (int)want);
@@ -306,6 +289,78 @@ int launch_colsum(const float* A, long long lda, long long nrows, int N, double*
     if (int rc = nplda_launch_status()) return rc;
     hipLaunchKernelGGL(xvbwd_colsum_finish_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, part, S, N, out);
     return nplda_launch_status();
+}
+
+}  // namespace
+
+// ---- the chains both training paths run (nplda_xvec_train.h) -------------------------------------------------------
+
+namespace nplda_xvec_train {
+
+int train_forward_head(const float* x, int layout, long long ld_in, const int64_t* offsets, long long U, long long R,
+                       const SavedLayout& L, char* saved, hipStream_t st) {
+    const long long T = layout == NPLDA_XVEC_LAYOUT_BCT ? R / U : 0;
+    const long long n0 = L.rows * kFeatP;
+    hipLaunchKernelGGL(xvec_prep_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, x, layout, ld_in, T, R,
+                       L.rows, (float*)(saved + L.oX));
+    if (int rc = nplda_launch_status()) return rc;
+    hipLaunchKernelGGL(xvtr_rem_kernel, dim3((unsigned)((L.rows + 255) / 256)), dim3(256), 0, st, offsets, U, R, L.rows,
+                       (int*)(saved + L.oRem));
+    if (int rc = nplda_launch_status()) return rc;
+    // slack rows: read by the last tile's taps here and by the weight gradient's (finite zeros, never NaN patterns)
+    for (int l = 0; l < kTdnn; ++l)
+        if (hipMemsetAsync(saved + L.oO[l] + (size_t)L.live * out_ld(l) * 4, 0, (size_t)kRowSlack * out_ld(l) * 4, st) !=
+            hipSuccess)
+            return NPLDA_EINVAL;
+    return NPLDA_OK;
+}
+
+int train_forward_tail(const float* P, const int64_t* offsets, long long U, long long R, int pooling,
+                       const SavedLayout& L, char* saved, float* out, long long ldx, hipStream_t st) {
+    float* pooled = (float*)(saved + L.oP);
+    hipLaunchKernelGGL(xvec_pool_kernel, dim3((unsigned)(U * kPoolBlocks)), dim3(256), 0, st,
+                       (const float*)(saved + L.oO[kTdnn - 1]), (long long)out_ld(kTdnn - 1), offsets, R, pooling, pooled);
+    if (int rc = nplda_launch_status()) return rc;
+    if (L.urows > U && hipMemsetAsync(pooled + U * kPooledLd, 0, (size_t)(L.urows - U) * kPooledLd * 4, st) != hipSuccess)
+        return NPLDA_EINVAL;
+    const GemmArgs a = gemm_args(P, geomF(kTdnn), pooled, kPooledLd, out, ldx, U, 1, 0);
+    return launch_gemm(xvtr_gemm_kernel<EpiExtract>, a, L.urows, st, EpiExtract{});
+}
+
+int backward_head(const BwdBuffers& b, const SavedLayout& L, long long U, const float* dxvec, long long lddx,
+                  const float* PT, float* grad, hipStream_t st, float** dA, long long* ldA) {
+    // dxvec -> (urows, 512) zero-padded
+    if (hipMemcpy2DAsync(b.dx, kEmbDim * 4, dxvec, (size_t)lddx * 4, kEmbDim * 4, (size_t)U, hipMemcpyDeviceToDevice,
+                         st) != hipSuccess)
+        return NPLDA_EINVAL;
+    if (L.urows > U && hipMemsetAsync(b.dx + U * kEmbDim, 0, (size_t)(L.urows - U) * kEmbDim * 4, st) != hipSuccess)
+        return NPLDA_EINVAL;
+    // lin11: dW11 = dxvec^T pooled, db11 = sum dxvec, dpooled = dxvec W11
+    float* g11 = grad + grad_offset(kTdnn);
+    if (int rc = launch_wgrad(kTdnn, b.dx, kEmbDim, kEmbDim, b.pooled, kPooledLd, U, b.part, g11, st)) return rc;
+    if (int rc = launch_colsum(b.dx, kEmbDim, U, kEmbDim, b.colp, g11 + (size_t)kEmbDim * kShape[kTdnn].Din, st))
+        return rc;
+    const GemmArgs a =
+        gemm_args(PT, geomT(kTdnn, packedT_offset(kTdnn)), b.dx, kEmbDim, b.dpool, kPooledLd, L.urows, 1, 0);
+    if (int rc = launch_gemm(xvtr_gemm_kernel<EpiExtract>, a, L.urows, st, EpiExtract{})) return rc;
+    // dA10 is written on the valid rows only (every other row zero); the ping-pong pair needs its leading rows zero
+    const int ld10 = out_ld(kTdnn - 1);
+    if (hipMemsetAsync(b.bufX, 0, (size_t)b.brow * ld10 * 4, st) != hipSuccess ||
+        hipMemsetAsync(b.bufY, 0, (size_t)kLead * kEmbDim * 4, st) != hipSuccess ||
+        hipMemsetAsync(b.bufZ, 0, (size_t)kLead * kEmbDim * 4, st) != hipSuccess)
+        return NPLDA_EINVAL;
+    *dA = b.bufX + (size_t)kLead * ld10;
+    *ldA = ld10;
+    return NPLDA_OK;
+}
+
+int layer_param_grads(int l, const float* dA, long long ldA, const BwdBuffers& b, const SavedLayout& L, float* grad,
+                      hipStream_t st) {
+    const Layer s = kShape[l];
+    const float* Oin = l == 0 ? (const float*)(b.sb + L.oX) : (const float*)(b.sb + L.oO[l - 1]);
+    const long long ldin = l == 0 ? kFeatP : out_ld(l - 1);
+    if (int rc = launch_wgrad(l, dA, ldA, (int)ldA, Oin, ldin, L.live, b.part, grad + grad_offset(l), st)) return rc;
+    return launch_colsum(dA, ldA, L.live, s.Dout, b.colp, grad + grad_offset(l) + (size_t)s.Dout * s.c * s.Din, st);
 }
 
 }  // namespace nplda_xvec_train
@@ -345,55 +400,29 @@ int nplda_xvec_pack_t_f32(const float* const* W, void* packed_t, size_t packed_t
 int nplda_xvec_extract_train_f32(const float* x, int layout, int64_t ld_in, const int64_t* offsets, int64_t n_utts,
                                  int64_t total_frames, int pooling, const void* packed, float* out, int64_t ldx,
                                  void* saved, size_t saved_bytes, nplda_stream_t stream) {
-    if (n_utts < 0 || total_frames < 0) return NPLDA_EINVAL;
-    if (layout != NPLDA_XVEC_LAYOUT_ROWS && layout != NPLDA_XVEC_LAYOUT_BCT) return NPLDA_EINVAL;
-    if (pooling != NPLDA_XVEC_POOL_STD && pooling != NPLDA_XVEC_POOL_VAR) return NPLDA_EINVAL;
-    if (n_utts == 0) return NPLDA_OK;
-    if (!x || !offsets || !packed || !out || !saved || !nplda_aligned16(packed) || !nplda_aligned16(out) ||
-        !nplda_aligned16(saved) || ldx < kEmbDim || (ldx % 4) != 0)
-        return NPLDA_EINVAL;
-    if (layout == NPLDA_XVEC_LAYOUT_ROWS && ld_in < kFeat) return NPLDA_EINVAL;
-    if (layout == NPLDA_XVEC_LAYOUT_BCT && (total_frames % n_utts) != 0) return NPLDA_EINVAL;
+    bool nothing;
+    const int bad = check_forward(n_utts, total_frames, layout, pooling, ld_in, ldx, {x, offsets, packed, out, saved},
+                                 {packed, out, saved}, &nothing);
+    if (bad || nothing) return bad;
     if (n_utts > 0x7fffffffLL / kPoolBlocks) return NPLDA_EUNSUPPORTED;
     const SavedLayout L = saved_layout(total_frames, n_utts);
     if (saved_bytes < L.total) return NPLDA_ENOSPC;
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)saved;
-    float* img = (float*)(base + L.oX);
-    int* rem = (int*)(base + L.oRem);
-    float* pooled = (float*)(base + L.oP);
+    const int* rem = (const int*)(base + L.oRem);
     const float* P = (const float*)packed;
-    const long long T = layout == NPLDA_XVEC_LAYOUT_BCT ? total_frames / n_utts : 0;
-    const long long n0 = L.rows * kFeatP;
-    hipLaunchKernelGGL(xvec_prep_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, x, layout,
-                       (long long)ld_in, T, (long long)total_frames, L.rows, img);
-    if (int rc = nplda_launch_status()) return rc;
-    hipLaunchKernelGGL(xvtr_rem_kernel, dim3((unsigned)((L.rows + 255) / 256)), dim3(256), 0, st, offsets,
-                       (long long)n_utts, (long long)total_frames, L.rows, rem);
-    if (int rc = nplda_launch_status()) return rc;
-    // slack rows: read by the last tile's taps here and by the weight gradient's (finite zeros, never NaN patterns)
-    for (int l = 0; l < kTdnn; ++l)
-        if (hipMemsetAsync(base + L.oO[l] + (size_t)L.live * out_ld(l) * 4, 0, (size_t)kRowSlack * out_ld(l) * 4, st) !=
-            hipSuccess)
-            return NPLDA_EINVAL;
-    const float* in = img;
+    if (int rc = train_forward_head(x, layout, ld_in, offsets, n_utts, total_frames, L, base, st)) return rc;
+    const float* in = (const float*)(base + L.oX);
     long long ld = kFeatP;
     for (int l = 0; l < kTdnn; ++l) {
         float* o = (float*)(base + L.oO[l]);
         const GemmArgs a = gemm_args(P, geomF(l), in, ld, o, out_ld(l), L.live, kShape[l].d, 1);
         const EpiTrain e{(uint8_t*)(base + L.oM[l]), (long long)out_ld(l), rem, kCtx[l]};
-        if (int rc = launch_gemm(a, L.live, e, st)) return rc;
+        if (int rc = launch_gemm(xvtr_gemm_kernel<EpiTrain>, a, L.live, st, e)) return rc;
         in = o;
         ld = out_ld(l);
     }
-    hipLaunchKernelGGL(xvec_pool_kernel, dim3((unsigned)(n_utts * kPoolBlocks)), dim3(256), 0, st, in, ld, offsets,
-                       (long long)total_frames, pooling, pooled);
-    if (int rc = nplda_launch_status()) return rc;
-    if (L.urows > n_utts &&
-        hipMemsetAsync(pooled + n_utts * kPooledLd, 0, (size_t)(L.urows - n_utts) * kPooledLd * 4, st) != hipSuccess)
-        return NPLDA_EINVAL;
-    const GemmArgs a = gemm_args(P, geomF(kTdnn), pooled, kPooledLd, out, ldx, n_utts, 1, 0);
-    return launch_gemm(a, L.urows, EpiExtract{}, st);
+    return train_forward_tail(P, offsets, n_utts, total_frames, pooling, L, base, out, ldx, st);
 }
 
 size_t nplda_xvec_grad_floats(void) { return grad_offset(kLayers); }
@@ -406,74 +435,34 @@ size_t nplda_xvec_backward_workspace_bytes(int64_t total_frames, int64_t n_utts)
 int nplda_xvec_backward_f32(const void* saved, size_t saved_bytes, const int64_t* offsets, int64_t n_utts,
                             int64_t total_frames, int pooling, const float* dxvec, int64_t lddx, const void* packed,
                             const void* packed_t, float* grad, void* ws, size_t ws_bytes, nplda_stream_t stream) {
-    if (n_utts < 0 || total_frames < 0) return NPLDA_EINVAL;
-    if (pooling != NPLDA_XVEC_POOL_STD && pooling != NPLDA_XVEC_POOL_VAR) return NPLDA_EINVAL;
-    if (n_utts == 0) return NPLDA_OK;
-    if (!saved || !offsets || !dxvec || !packed || !packed_t || !grad || !ws || !nplda_aligned16(saved) ||
-        !nplda_aligned16(packed) || !nplda_aligned16(packed_t) || !nplda_aligned16(grad) || !nplda_aligned16(ws) ||
-        lddx < kEmbDim)
-        return NPLDA_EINVAL;
+    bool nothing;
+    const int bad = check_backward(n_utts, total_frames, pooling, lddx, saved, offsets, dxvec, packed, packed_t, grad, ws,
+                                   &nothing);
+    if (bad || nothing) return bad;
     if (n_utts > 0x7fffffffLL / kPoolBlocks) return NPLDA_EUNSUPPORTED;
     const SavedLayout L = saved_layout(total_frames, n_utts);
     const WsLayoutB W = bwd_layout(total_frames, n_utts);
     if (saved_bytes < L.total || ws_bytes < W.total) return NPLDA_ENOSPC;
     hipStream_t st = (hipStream_t)stream;
-    const char* sb = (const char*)saved;
-    char* wb = (char*)ws;
+    const BwdBuffers b = bwd_buffers(L, W, saved, ws);
     const float* P = (const float*)packed;
     const float* PT = (const float*)packed_t;
-    float* dx = (float*)(wb + W.oDx);
-    float* dpool = (float*)(wb + W.oDp);
-    float* part = (float*)(wb + W.oPart);
-    double* colp = (double*)(wb + W.oCol);
-    const float* pooled = (const float*)(sb + L.oP);
-    const long long U = n_utts, brow = kLead + L.rows;
-    // dxvec -> (urows, 512) zero-padded
-    if (hipMemcpy2DAsync(dx, kEmbDim * 4, dxvec, (size_t)lddx * 4, kEmbDim * 4, (size_t)U, hipMemcpyDeviceToDevice,
-                         st) != hipSuccess)
-        return NPLDA_EINVAL;
-    if (L.urows > U && hipMemsetAsync(dx + U * kEmbDim, 0, (size_t)(L.urows - U) * kEmbDim * 4, st) != hipSuccess)
-        return NPLDA_EINVAL;
-    // lin11: dW11 = dxvec^T pooled, db11 = sum dxvec, dpooled = dxvec W11
-    if (int rc = launch_wgrad(kTdnn, dx, kEmbDim, kEmbDim, pooled, kPooledLd, U, part, grad + grad_offset(kTdnn), st))
-        return rc;
-    if (int rc = launch_colsum(dx, kEmbDim, U, kEmbDim, colp,
-                               grad + grad_offset(kTdnn) + (size_t)kEmbDim * kShape[kTdnn].Din, st))
-        return rc;
-    {
-        const GemmArgs a = gemm_args(PT, geomT(kTdnn, packedT_offset(kTdnn)), dx, kEmbDim, dpool, kPooledLd, L.urows, 1, 0);
-        if (int rc = launch_gemm(a, L.urows, EpiExtract{}, st)) return rc;
-    }
+    float* dA;
+    long long ldA;
+    if (int rc = backward_head(b, L, n_utts, dxvec, lddx, PT, grad, st, &dA, &ldA)) return rc;
     // tdnn10: pooling backward into dA10 (every other row zero)
-    const int ld10 = out_ld(kTdnn - 1);
-    float* bufX = (float*)(wb + W.oX);
-    float* bufY = (float*)(wb + W.oY);
-    float* bufZ = (float*)(wb + W.oZ);
-    if (hipMemsetAsync(bufX, 0, (size_t)brow * ld10 * 4, st) != hipSuccess ||
-        hipMemsetAsync(bufY, 0, (size_t)kLead * kEmbDim * 4, st) != hipSuccess ||
-        hipMemsetAsync(bufZ, 0, (size_t)kLead * kEmbDim * 4, st) != hipSuccess)
-        return NPLDA_EINVAL;
-    float* dA = bufX + (size_t)kLead * ld10;
-    hipLaunchKernelGGL(xvbwd_pool_kernel, dim3((unsigned)(U * kPoolBlocks)), dim3(256), 0, st,
-                       (const float*)(sb + L.oO[kTdnn - 1]), (long long)ld10, (const uint8_t*)(sb + L.oM[kTdnn - 1]),
-                       P + geomF(kTdnn - 1).oInv, pooled, dpool, offsets, (long long)total_frames, pooling, dA);
+    hipLaunchKernelGGL(xvbwd_pool_kernel, dim3((unsigned)(n_utts * kPoolBlocks)), dim3(256), 0, st,
+                       (const float*)(b.sb + L.oO[kTdnn - 1]), ldA, (const uint8_t*)(b.sb + L.oM[kTdnn - 1]),
+                       P + geomF(kTdnn - 1).oInv, b.pooled, b.dpool, offsets, (long long)total_frames, pooling, dA);
     if (int rc = nplda_launch_status()) return rc;
-    long long ldA = ld10;
     for (int l = kTdnn - 1; l >= 0; --l) {
-        const Layer s = kShape[l];
-        const float* Oin = l == 0 ? (const float*)(sb + L.oX) : (const float*)(sb + L.oO[l - 1]);
-        const long long ldin = l == 0 ? kFeatP : out_ld(l - 1);
-        if (int rc = launch_wgrad(l, dA, ldA, (int)ldA, Oin, ldin, L.live, part, grad + grad_offset(l), st)) return rc;
-        if (int rc = launch_colsum(dA, ldA, L.live, s.Dout, colp, grad + grad_offset(l) + (size_t)s.Dout * s.c * s.Din,
-                                   st))
-            return rc;
+        if (int rc = layer_param_grads(l, dA, ldA, b, L, grad, st)) return rc;
         if (l == 0) break;
-        float* nxt = ((kTdnn - 1 - l) & 1 ? bufZ : bufY) + (size_t)kLead * kEmbDim;
-        const EpiBwd e{(const uint8_t*)(sb + L.oM[l - 1]), (long long)out_ld(l - 1), P + geomF(l - 1).oInv};
-        const GemmArgs a = gemm_args(PT, geomT(l, packedT_offset(l)), dA, ldA, nxt, kEmbDim, L.live, -s.d, 0);
-        if (int rc = launch_gemm(a, L.live, e, st)) return rc;
-        dA = nxt;
-        ldA = kEmbDim;
+        const EpiBwd e{(const uint8_t*)(b.sb + L.oM[l - 1]), (long long)out_ld(l - 1), P + geomF(l - 1).oInv};
+        const GemmArgs a = data_grad_args(l, PT, dA, ldA, b, L.live);
+        if (int rc = launch_gemm(xvtr_gemm_kernel<EpiBwd>, a, L.live, st, e)) return rc;
+        dA = a.out;
+        ldA = a.ld_out;
     }
     return NPLDA_OK;
 }

@@ -1,7 +1,10 @@
 // nplda_xvec_train.h — what the two training paths of the E-TDNN extractor share: the running-statistics path
-// (nplda_xvec_bwd.hip) and the batch-statistics path (nplda_xvec_bn.hip).  Buffer layouts and index helpers are inline;
-// the launchers of the weight-gradient, column-sum, plain-store GEMM and row-index kernels are defined once, in
-// nplda_xvec_bwd.hip, next to their kernels (the library's version script keeps them out of the dynamic symbol table).
+// (nplda_xvec_bwd.hip) and the batch-statistics path (nplda_xvec_bn.hip).  Buffer layouts, index helpers and the argument
+// checks of a backward entry point are inline.  The two chains are defined once, in nplda_xvec_bwd.hip, next to their
+// kernels (the library's version script keeps them out of the dynamic symbol table): the training forward is
+// train_forward_head, the caller's own layer loop, train_forward_tail; a backward is backward_head, the caller's pooling
+// backward, then per layer the caller's batch-norm step if any, layer_param_grads, and the caller's data-gradient GEMM on
+// data_grad_args.
 #pragma once
 #include "nplda_xvec_body.h"
 
@@ -15,9 +18,6 @@ constexpr int kWgKC = 16;     // frames per staged wgrad chunk
 constexpr int kWgTargetBlocks = 512;
 constexpr int kColSplits = 1024;  // row splits of the bias column sums (enough blocks to stream dA at bandwidth)
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-inline int out_ld(int l) { return l == kTdnn - 1 ? 16 * ((kPoolDim + 15) / 16) : kEmbDim; }
-
 // the transposed image holds layers 1..10 (tdnn2..tdnn10, lin11): per tap the Dout x Din block transposed
 inline LayerGeom geomT(int l, size_t start) {
     const Layer s = kShape[l];
@@ -29,11 +29,6 @@ inline size_t packedT_offset(int l) {
     return o;
 }
 inline size_t packedT_floats() { return packedT_offset(kLayers); }
-inline LayerGeom geomF(int l) {
-    size_t o = 0;
-    for (int i = 0; i < l; ++i) o = geom(i, o).end;
-    return geom(l, o);
-}
 
 // flat gradient: for l = 0..10, W_l (Dout, c Din) then b_l (Dout)
 inline size_t grad_offset(int l) {
@@ -49,9 +44,9 @@ struct SavedLayout {
 
 inline SavedLayout saved_layout(long long R, long long U) {
     SavedLayout s;
-    s.live = (R + kRowsPerBlock - 1) / kRowsPerBlock * kRowsPerBlock;
+    s.live = whole_tiles(R);
     s.rows = s.live + kRowSlack;
-    s.urows = (U + kRowsPerBlock - 1) / kRowsPerBlock * kRowsPerBlock;
+    s.urows = whole_tiles(U);
     size_t o = 0;
     s.oX = o;
     o = align256(o + (size_t)s.rows * kFeatP * 4);
@@ -124,28 +119,65 @@ inline WsLayoutB bwd_layout(long long R, long long U) {
     return w;
 }
 
-inline GemmArgs gemm_args(const float* img, const LayerGeom& G, const float* in, long long ld_in, float* out,
-                          long long ld_out, long long row_limit, int dil, int relu_bn) {
-    GemmArgs a;
-    a.in = in; a.ld_in = ld_in;
-    a.frag = reinterpret_cast<const f32x4*>(img + G.oFrag);
-    a.bias = img + G.oBias; a.mean = img + G.oMean; a.inv = img + G.oInv;
-    a.out = out; a.ld_out = ld_out; a.row_limit = row_limit;
-    a.nkb = G.nkb; a.nkbp = G.nkbp; a.XBp = G.XBp; a.Np = G.Np; a.kbt = G.Dinp / 16; a.dil = dil;
-    a.relu_bn = relu_bn;
-    return a;
+// The argument checks of a backward entry point, in the order that is part of the ABI; the caller's grid limits
+// (EUNSUPPORTED) and buffer sizes (ENOSPC) follow them, in that order.  *nothing: n_utts == 0, return OK.
+inline int check_backward(int64_t n_utts, int64_t total_frames, int pooling, int64_t lddx, const void* saved,
+                          const void* offsets, const void* dxvec, const void* packed, const void* packed_t,
+                          const void* grad, const void* ws, bool* nothing) {
+    *nothing = false;
+    if (n_utts < 0 || total_frames < 0) return NPLDA_EINVAL;
+    if (bad_pooling(pooling)) return NPLDA_EINVAL;
+    *nothing = n_utts == 0;
+    if (*nothing) return NPLDA_OK;
+    if (!none_null({saved, offsets, dxvec, packed, packed_t, grad, ws}) ||
+        !all_aligned16({saved, packed, packed_t, grad, ws}) || lddx < kEmbDim)
+        return NPLDA_EINVAL;
+    return NPLDA_OK;
 }
 
-// ---- launchers defined in nplda_xvec_bwd.hip ---------------------------------------------------------------------
+// the backward's buffers, carved from the caller's `saved` (read) and workspace (written)
+struct BwdBuffers {
+    const char* sb;            // saved
+    float *dx, *dpool;         // dxvec zero-padded to (urows, 512); dpooled (urows, 3008)
+    float* part;               // split-K partials of the weight gradients
+    double* colp;              // partials of the bias column sums
+    float *bufX, *bufY, *bufZ; // brow rows each: dA10 (ld 1504), and the ping-pong pair of dA9..dA1 (ld 512)
+    const float* pooled;
+    long long brow;            // kLead zeroed rows, then the saved rows
+};
 
-// rem[r] = frames left in row r's utterance (this one included), 0 outside every utterance, for r < rows
-int launch_rem(const int64_t* offsets, long long U, long long R, long long rows, int* rem, hipStream_t st);
-// the GEMM with the extraction epilogue (bias, and ReLU / running-statistics batch norm when a.relu_bn)
-int launch_gemm_extract(const GemmArgs& a, long long rows, hipStream_t st);
-// dW_l (torch layout) from dA rows and the layer's input rows: split-K partials in `part`, summed in split order
-int launch_wgrad(int l, const float* A, long long lda, int acols, const float* B, long long ldb, long long kmax,
-                 float* part, float* out, hipStream_t st);
-// out[col] = sum over nrows of A[:, col]: fp64 partials in `part` (kColSplits x N doubles at most), fixed order
-int launch_colsum(const float* A, long long lda, long long nrows, int N, double* part, float* out, hipStream_t st);
+inline BwdBuffers bwd_buffers(const SavedLayout& L, const WsLayoutB& W, const void* saved, void* ws) {
+    const char* sb = (const char*)saved;
+    char* wb = (char*)ws;
+    return BwdBuffers{sb, (float*)(wb + W.oDx), (float*)(wb + W.oDp), (float*)(wb + W.oPart), (double*)(wb + W.oCol),
+                      (float*)(wb + W.oX), (float*)(wb + W.oY), (float*)(wb + W.oZ), (const float*)(sb + L.oP),
+                      kLead + L.rows};
+}
+
+// The data gradient of layer l (tdnn<l+1>, l >= 1): dA_l at dA, the layer's transposed image, negative taps; the result
+// goes to a.out = the ping-pong buffer of dA_{l-1} behind its kLead zeroed rows, row stride 512.
+inline GemmArgs data_grad_args(int l, const float* PT, const float* dA, long long ldA, const BwdBuffers& b,
+                               long long live) {
+    float* nxt = ((kTdnn - 1 - l) & 1 ? b.bufZ : b.bufY) + (size_t)kLead * kEmbDim;
+    return gemm_args(PT, geomT(l, packedT_offset(l)), dA, ldA, nxt, kEmbDim, live, -kShape[l].d, 0);
+}
+
+// ---- defined in nplda_xvec_bwd.hip ---------------------------------------------------------------------------------
+
+// Training forward, before the layer loop: the padded input image, rem[r] = frames left in row r's utterance (this one
+// included, 0 outside every utterance), and the zeroed slack rows of the ten activation buffers of `saved`.
+int train_forward_head(const float* x, int layout, long long ld_in, const int64_t* offsets, long long U, long long R,
+                       const SavedLayout& L, char* saved, hipStream_t st);
+// Training forward, after the layer loop: statistics pooling of the tdnn10 rows of `saved` into its pooled rows (padded
+// with zero rows to whole tiles) and lin11 with the extraction epilogue into out.
+int train_forward_tail(const float* P, const int64_t* offsets, long long U, long long R, int pooling,
+                       const SavedLayout& L, char* saved, float* out, long long ldx, hipStream_t st);
+// Backward, before the pooling backward: dxvec zero-padded, dW11 = dxvec^T pooled, db11 = sum dxvec, dpooled = dxvec W11
+// (b.dpool), and the zeroed bufX and leading rows of bufY / bufZ.  *dA, *ldA: where dA10 goes (bufX behind its lead).
+int backward_head(const BwdBuffers& b, const SavedLayout& L, long long U, const float* dxvec, long long lddx,
+                  const float* PT, float* grad, hipStream_t st, float** dA, long long* ldA);
+// dW_l and db_l of tdnn<l+1> from dA_l and the layer's saved input rows
+int layer_param_grads(int l, const float* dA, long long ldA, const BwdBuffers& b, const SavedLayout& L, float* grad,
+                      hipStream_t st);
 
 }  // namespace nplda_xvec_train

@@ -354,8 +354,7 @@ class XVectorNet_ETDNN_12Layer(nn.Module):
                                f"the limit of {limit} bytes; the statistics span the batch, so it is not split")
         if grad:
             return _ExtractBnFn.apply(self, X, layout, lengths, dev, *self._grad_params())
-        out, _ = _bn_forward(self, X, layout, lengths, dev)
-        return out
+        return _bn_forward(self, X, layout, lengths, dev)[0]
 
     # -- extraction ------------------------------------------------------------------------------
     def _run(self, x, layout, lengths, dev, workspace_bytes):
@@ -614,48 +613,65 @@ class XVectorNet_ETDNN_12Layer(nn.Module):
         self.invalidate_packed()
 
 
+def _train_call(ext, lengths, dev):
+    """What a training forward starts from -> (U, R, pooling kind, utterance offsets on the device, empty output).
+    The copy of the offsets waits for the stream: call this after the host work (packed images), next to the C call."""
+    U, R = len(lengths), int(sum(lengths))
+    starts = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    out = torch.empty((U, XVEC_DIM), dtype=torch.float32, device=dev)
+    with _lib.on_device(dev):
+        offs = torch.from_numpy(starts).to(dev)
+    return U, R, _pool_kind(ext.pooling_function), offs, out
+
+
+def _split_grad(grad, shapes):
+    """The flat gradient of the C ABI -> one view per parameter (`_grad_params` order)."""
+    grads, o = [], 0
+    for sh in shapes:
+        k = int(np.prod(sh))
+        grads.append(grad[o:o + k].view(sh))
+        o += k
+    return tuple(grads)
+
+
+def _backward(ctx, dout, ws_bytes, backward):
+    """One backward call on what the forward kept in ctx.state (dropped here): `ws_bytes` and `backward` name the path's
+    C entry points, the state's last entry is its workspace allocator (n, dev) or None.  -> Function.backward's result."""
+    saved, offs, packed, packed_t, R, U, kind, dev, shapes, alloc = ctx.state
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        d = dout.detach().to(dev, torch.float32).contiguous()
+        grad = torch.empty(lib.nplda_xvec_grad_floats(), dtype=torch.float32, device=dev)
+        n = getattr(lib, ws_bytes)(R, U)
+        ws = torch.empty(n, dtype=torch.uint8, device=dev) if alloc is None else alloc(n, dev)
+        _lib.check(getattr(lib, backward)(saved.data_ptr(), saved.numel(), offs.data_ptr(), U, R, kind, d.data_ptr(),
+                                          XVEC_DIM, packed.data_ptr(), packed_t.data_ptr(), grad.data_ptr(),
+                                          ws.data_ptr(), n, _lib.current_stream(dev)), backward)
+    ctx.state = None
+    return (None,) * 5 + _split_grad(grad, shapes)
+
+
 class _ExtractFn(torch.autograd.Function):
     """extract / extract_ragged with a backward to the 22 tdnn1..tdnn10 / lin11 parameters (inputs after the first
     five, in `_grad_params` order).  The saved buffer (~30 KB per frame) lives from forward to backward."""
 
     @staticmethod
     def forward(ctx, ext, X, layout, lengths, dev, *params):
-        U, R = len(lengths), int(sum(lengths))
-        kind = _pool_kind(ext.pooling_function)
         packed, packed_t = ext._packed(dev), ext._packed_t(dev)
         lib = _lib.load()
-        starts = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
-        out = torch.empty((U, XVEC_DIM), dtype=torch.float32, device=dev)
+        U, R, kind, offs, out = _train_call(ext, lengths, dev)
         with _lib.on_device(dev):
-            offs = torch.from_numpy(starts).to(dev)
             n = lib.nplda_xvec_train_saved_bytes(R, U)
             saved = torch.empty(n, dtype=torch.uint8, device=dev)
             _lib.check(lib.nplda_xvec_extract_train_f32(X.data_ptr(), layout, FEAT, offs.data_ptr(), U, R, kind,
                                                         packed.data_ptr(), out.data_ptr(), XVEC_DIM, saved.data_ptr(), n,
                                                         _lib.current_stream(dev)), "nplda_xvec_extract_train_f32")
-        ctx.state = (saved, offs, packed, packed_t, R, U, kind, dev, [tuple(p.shape) for p in params])
+        ctx.state = (saved, offs, packed, packed_t, R, U, kind, dev, [tuple(p.shape) for p in params], None)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        saved, offs, packed, packed_t, R, U, kind, dev, shapes = ctx.state
-        lib = _lib.load()
-        with _lib.on_device(dev):
-            d = dout.detach().to(dev, torch.float32).contiguous()
-            grad = torch.empty(lib.nplda_xvec_grad_floats(), dtype=torch.float32, device=dev)
-            n = lib.nplda_xvec_backward_workspace_bytes(R, U)
-            ws = torch.empty(n, dtype=torch.uint8, device=dev)
-            _lib.check(lib.nplda_xvec_backward_f32(saved.data_ptr(), saved.numel(), offs.data_ptr(), U, R, kind,
-                                                   d.data_ptr(), XVEC_DIM, packed.data_ptr(), packed_t.data_ptr(),
-                                                   grad.data_ptr(), ws.data_ptr(), n, _lib.current_stream(dev)),
-                       "nplda_xvec_backward_f32")
-        grads, o = [], 0
-        for sh in shapes:
-            k = int(np.prod(sh))
-            grads.append(grad[o:o + k].view(sh))
-            o += k
-        ctx.state = None
-        return (None,) * 5 + tuple(grads)
+        return _backward(ctx, dout, "nplda_xvec_backward_workspace_bytes", "nplda_xvec_backward_f32")
 
 
 def _bn_buffer(ext, n, dev, what):
@@ -665,16 +681,12 @@ def _bn_buffer(ext, n, dev, what):
 def _bn_forward(ext, X, layout, lengths, dev):
     """One nplda_xvec_extract_train_bn_f32 call over the whole batch, then torch's running-statistics update on the
     module's buffers (in-place torch ops, so that the packed-image cache, keyed on their versions, notices).
-    -> (x-vectors, state for _ExtractBnFn.backward)."""
-    U, R = len(lengths), int(sum(lengths))
-    kind = _pool_kind(ext.pooling_function)
+    -> (x-vectors, (saved, offs, packed, R, U, kind, dev): what _ExtractBnFn keeps for its backward)."""
     packed = ext._packed(dev)
     lib = _lib.load()
-    starts = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
-    out = torch.empty((U, XVEC_DIM), dtype=torch.float32, device=dev)
     bns = [t.bn for t in ext.tdnns()]
+    U, R, kind, offs, out = _train_call(ext, lengths, dev)
     with _lib.on_device(dev):
-        offs = torch.from_numpy(starts).to(dev)
         n = lib.nplda_xvec_train_bn_saved_bytes(R, U)
         saved = _bn_buffer(ext, n, dev, "saved")
         ns = lib.nplda_xvec_bn_stats_bytes()
@@ -706,30 +718,14 @@ class _ExtractBnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ext, X, layout, lengths, dev, *params):
         packed_t = ext._packed_t(dev)  # (before the update of the running statistics drops the cache entry)
-        out, state = _bn_forward(ext, X, layout, lengths, dev)
-        ctx.state = state + (packed_t, ext, [tuple(p.shape) for p in params])
+        out, kept = _bn_forward(ext, X, layout, lengths, dev)
+        ctx.state = kept[:3] + (packed_t,) + kept[3:] + ([tuple(p.shape) for p in params],
+                                                         lambda n, dev: _bn_buffer(ext, n, dev, "ws"))
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        saved, offs, packed, R, U, kind, dev, packed_t, ext, shapes = ctx.state
-        lib = _lib.load()
-        with _lib.on_device(dev):
-            d = dout.detach().to(dev, torch.float32).contiguous()
-            grad = torch.empty(lib.nplda_xvec_grad_floats(), dtype=torch.float32, device=dev)
-            n = lib.nplda_xvec_backward_bn_workspace_bytes(R, U)
-            ws = _bn_buffer(ext, n, dev, "ws")
-            _lib.check(lib.nplda_xvec_backward_bn_f32(saved.data_ptr(), saved.numel(), offs.data_ptr(), U, R, kind,
-                                                      d.data_ptr(), XVEC_DIM, packed.data_ptr(), packed_t.data_ptr(),
-                                                      grad.data_ptr(), ws.data_ptr(), n, _lib.current_stream(dev)),
-                       "nplda_xvec_backward_bn_f32")
-        grads, o = [], 0
-        for sh in shapes:
-            k = int(np.prod(sh))
-            grads.append(grad[o:o + k].view(sh))
-            o += k
-        ctx.state = None
-        return (None,) * 5 + tuple(grads)
+        return _backward(ctx, dout, "nplda_xvec_backward_bn_workspace_bytes", "nplda_xvec_backward_bn_f32")
 
 
 class Etdnn_Xvec_NeuralPlda(NeuralPlda):

@@ -1,17 +1,16 @@
 """CPU tests of the E-TDNN x-vector extractor's host side: the fp64 restatement against the reference-generated fixture
 (g13), state-dict layout, Kaldi pickle loading, pickling through the compat aliases, E2EConf, argument checks, the
 workspace restatement and the GEMM kernel's resource budget."""
+import ctypes
 import os
 import pickle
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from tests import xvec_ref
+from tests.test_allpairs_cpu import _resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G13 = os.path.join(ROOT, "tests", "golden", "g13_etdnn.npz")
@@ -221,25 +220,124 @@ def test_xvec_abi_argument_checks(hip_lib):
     assert hip_lib.nplda_xvec_extract_f32(None, 0, 30, None, 1, 40, 0, None, None, 512, None, 0, None) == -22
 
 
+# ---- status table of the six extractor entry points --------------------------------------------------------------------
+# Every row returns before anything is enqueued, so the pointers are fake addresses that nothing dereferences: _A is
+# 16-byte aligned, _M is not.  A size argument is given as a difference from what the library asks for at the row's
+# (total_frames, n); the base vector passes every check but the last: each buffer is one byte short (-28).  A row changes
+# the base in one place, so a check that moved behind the size test would show as -28.
+# Rows per entry point (the test asserts these counts, so a row cannot drop out unseen), by expected status:
+#   extract, extract_train, backward   29 rows: 20 x -22, 7 x -28, 1 x -95, 1 x 0
+#   extract_windows                    27 rows: 18 x -22, 7 x -28, 1 x -95, 1 x 0   (no layout argument)
+#   extract_train_bn                   38 rows: 26 x -22, 9 x -28, 2 x -95, 1 x 0   (eps, stats; rows; frame limit)
+#   backward_bn                        33 rows: 22 x -22, 8 x -28, 2 x -95, 1 x 0
+_ROWS = {"extract": 29, "extract_train": 29, "backward": 29, "extract_windows": 27, "extract_train_bn": 38,
+         "backward_bn": 33}
+_A, _M = 4096, 4096 + 8
+_EPS = (ctypes.c_float * 10)(*[1e-5] * 10)
+_FWD = ("x", "layout", "ld_in", "offsets", "n", "total_frames", "pooling", "packed", "out", "ldx")
+_BWD = ("saved", "saved_bytes", "offsets", "n", "total_frames", "pooling", "dxvec", "lddx", "packed", "packed_t", "grad",
+        "ws", "ws_bytes", "stream")
+_ENTRIES = {
+    "extract": dict(
+        fn="nplda_xvec_extract_f32", args=_FWD + ("ws", "ws_bytes", "stream"),
+        sizes={"ws_bytes": "nplda_xvec_workspace_bytes"}, ptrs=("x", "offsets", "packed", "out", "ws"),
+        aligned=("packed", "out", "ws"), limit=0x7fffffff // 6),
+    "extract_windows": dict(
+        fn="nplda_xvec_extract_windows_f32",
+        args=("x", "ld_in", "total_frames", "win_begin", "win_end", "n", "pooling", "packed", "out", "ldx", "ws", "ws_bytes",
+              "stream"),
+        sizes={"ws_bytes": "nplda_xvec_windows_workspace_bytes"},
+        ptrs=("x", "win_begin", "win_end", "packed", "out", "ws"), aligned=("packed", "out", "ws"), limit=0x7fffffff // 3),
+    "extract_train": dict(
+        fn="nplda_xvec_extract_train_f32", args=_FWD + ("saved", "saved_bytes", "stream"),
+        sizes={"saved_bytes": "nplda_xvec_train_saved_bytes"}, ptrs=("x", "offsets", "packed", "out", "saved"),
+        aligned=("packed", "out", "saved"), limit=0x7fffffff // 6),
+    "extract_train_bn": dict(
+        fn="nplda_xvec_extract_train_bn_f32",
+        args=_FWD[:8] + ("eps",) + _FWD[8:] + ("saved", "saved_bytes", "stats", "stats_bytes", "stream"),
+        sizes={"saved_bytes": "nplda_xvec_train_bn_saved_bytes", "stats_bytes": "nplda_xvec_bn_stats_bytes"},
+        ptrs=("x", "offsets", "packed", "eps", "out", "saved", "stats"), aligned=("packed", "out", "saved", "stats"),
+        limit=0x7fffffff // 6, batch_stats=True),
+    "backward": dict(
+        fn="nplda_xvec_backward_f32", args=_BWD,
+        sizes={"saved_bytes": "nplda_xvec_train_saved_bytes", "ws_bytes": "nplda_xvec_backward_workspace_bytes"},
+        ptrs=("saved", "offsets", "dxvec", "packed", "packed_t", "grad", "ws"),
+        aligned=("saved", "packed", "packed_t", "grad", "ws"), limit=0x7fffffff // 6),
+    "backward_bn": dict(
+        fn="nplda_xvec_backward_bn_f32", args=_BWD,
+        sizes={"saved_bytes": "nplda_xvec_train_bn_saved_bytes", "ws_bytes": "nplda_xvec_backward_bn_workspace_bytes"},
+        ptrs=("saved", "offsets", "dxvec", "packed", "packed_t", "grad", "ws"),
+        aligned=("saved", "packed", "packed_t", "grad", "ws"), limit=0x7fffffff // 6, batch_stats=True),
+}
+
+
+def _status_rows(e):
+    """(what, changes to the base vector, expected status), from reading the checks of the entry point in order."""
+    fwd, layout, bn = "ldx" in e["args"], "layout" in e["args"], e.get("batch_stats", False)
+    big = e["limit"] + 1
+    rows = [("base: every buffer one byte short", {}, -28),
+            ("negative n", {"n": -1}, -22),
+            ("negative total_frames", {"total_frames": -1}, -22),
+            ("bad pooling", {"pooling": 2}, -22),
+            ("bad pooling comes before the n == 0 return", {"pooling": 2, "n": 0, "total_frames": 0}, -22),
+            ("n == 0: nothing to do, no pointer is looked at",
+             dict({p: None for p in e["ptrs"]}, n=0, total_frames=0), 0),
+            ("n above the grid limit", {"n": big, "total_frames": 25 * big}, -95),
+            ("null pointer and n above the grid limit: the pointer check wins",
+             {e["ptrs"][0]: None, "n": big, "total_frames": 25 * big}, -22)]
+    if layout:
+        rows += [("bad layout", {"layout": 2}, -22),
+                 ("bad layout comes before the n == 0 return", {"layout": 2, "n": 0, "total_frames": 0}, -22),
+                 ("ld_in of 29", {"ld_in": 29}, -22),
+                 ("BCT ignores ld_in", {"layout": 1, "total_frames": 735, "ld_in": 29}, -28),
+                 ("BCT, total_frames % n != 0", {"layout": 1, "total_frames": 734}, -22)]
+    elif fwd:
+        rows += [("ld_in of 29", {"ld_in": 29}, -22)]
+    rows += [(f"null {p}", {p: None}, -22) for p in e["ptrs"]]
+    rows += [(f"misaligned {p}", {p: _M}, -22) for p in e["aligned"]]
+    rows += [(f"{p} needs no alignment", {p: _M}, -28) for p in e["ptrs"] if p not in e["aligned"] and p != "eps"]
+    if fwd:
+        rows += [("ldx of 511", {"ldx": 511}, -22), ("ldx of 514", {"ldx": 514}, -22), ("ldx of 516", {"ldx": 516}, -28)]
+    else:
+        rows += [("lddx of 511", {"lddx": 511}, -22), ("lddx of 514", {"lddx": 514}, -28)]
+    if bn:
+        rows += [("too few rows: R - 22 n == 1", {"total_frames": 111}, -22),
+                 ("just enough rows", {"total_frames": 112}, -28),
+                 ("too few rows and n above the grid limit: the row count wins", {"n": big, "total_frames": 22 * big}, -22),
+                 ("total_frames above the grid limit of the row kernels", {"total_frames": 0x7fffffff * 16 - 127}, -95),
+                 ("total_frames at that limit", {"total_frames": 0x7fffffff * 16 - 128}, -28)]
+    else:
+        rows += [("no lower bound on the rows", {"total_frames": 111}, -28)]
+    for s in e["sizes"]:
+        rows.append((f"only {s} one byte short", {k: (-1 if k == s else 0) for k in e["sizes"]}, -28))
+        rows.append((f"null pointer and {s} short: the pointer check wins",
+                     dict({k: (-1 if k == s else 0) for k in e["sizes"]}, **{e["ptrs"][-1]: None}), -22))
+    return rows
+
+
+@pytest.mark.parametrize("entry", sorted(_ENTRIES))
+def test_xvec_entry_point_status_table(hip_lib, entry):
+    """Every argument check of the six extractor entry points, in the order the entry point makes them: one row per check
+    with everything before it passing, and rows where two fail and the earlier one must win."""
+    e = _ENTRIES[entry]
+    fn = getattr(hip_lib, e["fn"])
+    rows = _status_rows(e)
+    assert len(rows) == _ROWS[entry], (entry, len(rows))
+    for what, change, want in rows:
+        v = dict({p: _A for p in e["ptrs"]}, eps=_EPS, layout=0, ld_in=30, n=5, total_frames=733, pooling=0, ldx=512,
+                 lddx=512, stream=None)
+        v.update({k: -1 for k in e["sizes"]})
+        v.update(change)
+        R, n = max(v["total_frames"], 0), max(v["n"], 0)
+        for k, size_fn in e["sizes"].items():
+            f = getattr(hip_lib, size_fn)
+            v[k] = max((f(R, n) if f.argtypes else f()) + v[k], 0)
+        assert fn(*[v[a] for a in e["args"]]) == want, (entry, what)
+
+
 def test_xvec_gemm_kernel_resources():
     """The TDNN GEMM keeps two blocks per CU (64 KB of LDS each, <= 256 registers) with nothing in scratch."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "neuralplda_amd", "csrc")
-    err = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", os.path.join(csrc, "nplda_xvec.hip"),
-                          "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True,
-                         timeout=900).stderr
-    res, cur = {}, None
-    for line in err.splitlines():
-        m = re.search(r"remark: +(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|"
-                      r"LDS Size \[bytes/block\]): +(\S+)", line)
-        if not m:
-            continue
-        if m.group(1) == "Function Name":
-            cur = res.setdefault(m.group(2), {})
-        elif cur is not None:
-            cur[m.group(1).split(" ")[0]] = int(m.group(2))
+    res = _resources("nplda_xvec.hip")
     gemm = [v for k, v in res.items() if "xvec_gemm_kernel" in k]
     assert len(gemm) == 1, sorted(res)
     g = gemm[0]

@@ -4,15 +4,13 @@ Etdnn_Xvec_NeuralPlda.train1(finetune_extractor=...)) and the fp64 torch restate
 reference-generated fixture g14."""
 import os
 import pickle
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from tests import xvec_grad_ref as gref, xvec_ref
+from tests.test_allpairs_cpu import _resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G13 = os.path.join(ROOT, "tests", "golden", "g13_etdnn.npz")
@@ -94,23 +92,7 @@ def test_backward_abi_argument_checks(hip_lib):
 
 def test_backward_kernel_resources():
     """Every kernel of nplda_xvec_bwd.hip runs without scratch; the GEMMs keep at least two blocks per CU."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "neuralplda_amd", "csrc")
-    err = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c",
-                          os.path.join(csrc, "nplda_xvec_bwd.hip"), "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900).stderr
-    res, cur = {}, None
-    for line in err.splitlines():
-        m = re.search(r"remark: +(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|"
-                      r"LDS Size \[bytes/block\]): +(\S+)", line)
-        if not m:
-            continue
-        if m.group(1) == "Function Name":
-            cur = res.setdefault(m.group(2), {})
-        elif cur is not None:
-            cur[m.group(1).split(" ")[0]] = int(m.group(2))
+    res = _resources("nplda_xvec_bwd.hip")
     gemms = {k: v for k, v in res.items() if "xvtr_gemm_kernel" in k or "xvbwd_wgrad_kernel" in k}
     assert len(gemms) == 4, sorted(res)  # EpiTrain, EpiBwd, EpiExtract, wgrad
     for k, v in gemms.items():
